@@ -24,10 +24,26 @@ carries the replica throughput as the headline and says so.
 ``--shard host`` runs the sharded sort over the gloo host transport (a
 rehearsal on one GPU: SFHE_BENCH_DEVICE=0 puts every rank on it).
 
-Extra fields: ``roofline`` (dominant kernel family: HIP events around each of
+A plain run does only what the headline needs: set up the engine and the
+sorter, warm up, time the K steps, write the outputs if asked, print the line.
+
+``--dump-outputs DIR``: after the timed steps, what the last timed step
+computed, as ``DIR/<name>.npy`` (float64): ``sorted`` = the output ciphertext
+of that ``DirectSort<N>::sort`` decrypted with the run's own key (every slot
+the engine returns: what a caller of the sort receives once it decrypts), and
+``level`` = that ciphertext's level.  Keys, input and encryption randomness
+are seeded by the workload alone, so the same arguments give the same inputs
+in every run.  The residues of the ciphertext itself are not written: they are
+a key- and noise-dependent encoding that two correct builds need not share.
+
+``--full`` adds, after the timed region, everything else the benchmark
+measures: ``roofline`` (dominant kernel family: HIP events around each of
 its launches during one profiling sort after the timed region, lanes
-serialised as under rocprofv3), ``cpu_baseline`` (one real DirectSort<N> on
-the C oracle, rank 0 only, N=1 only) and ``trials`` (pure / as-test / cold).
+serialised as under rocprofv3), ``kernels`` / ``graph_breakdown`` /
+``batched_ops``, ``trials`` (pure / as-test / cold), the config-5, hybrid1 and
+k-way legs, and ``cpu_baseline`` (one real DirectSort<N> on the C oracle, rank
+0 only, N=1 only).  ``--trials`` and the ``--no-*`` / ``--c5-eager`` options
+select among these and have no effect without ``--full``.
 """
 from __future__ import annotations
 
@@ -386,12 +402,37 @@ def fallback_line(replicas, spec, world, args, why):
             "replicas": replicas, "sharded_error": why}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, eng, out, write: bool):
+    """--dump-outputs: the last timed step's output ciphertext, decrypted, and
+    its level, as float64 .npy files.  Every rank decrypts (a sharded engine
+    gathers the limbs); `write` says whether this rank saves the files."""
+    import numpy as np
+    arrays = {"sorted": np.asarray(eng.decrypt(out), dtype=np.float64),
+              "level": np.array([out.level], dtype=np.float64)}
+    # at most ring_dim / 2 slots: far below the limit for every workload
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    if write:
+        os.makedirs(directory, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="directsort_n256_2e16", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the sorted "
+                         "array as decrypted, and the ciphertext's level) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the profiling sort (roofline, per-kernel figures), "
+                         "the per-sort trials, the config-5 / hybrid1 / k-way legs and the CPU baseline; "
+                         "the options below select among these and need --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--trials", type=int, default=10,
                     help="per-sort trials after the timed region (median/min/max, pure and as-test)")
@@ -472,11 +513,15 @@ def main(argv=None):
     kernel_name = {"ntt": "k_ntt (both passes, fwd+inv)", "conv": "k_convf / k_mdrsf",
                    "ks_inner": "k_ks_inner", "ntt_ks": "k_ntt_ks (ModUp ROW pass + key inner product)"}
 
-    def step():
-        out = sorter.sort(ct, *cfg)
-        del out
+    last = {}
 
-    # cold sort: a fresh sorter's first sort (host mask generation + encoding)
+    def step():
+        last.clear()  # one output alive at a time
+        last["out"] = sorter.sort(ct, *cfg)
+
+    # setup: a fresh sorter's first sort generates and encodes the masks on the
+    # host and runs eagerly, so it precedes the warmup in every run; its time
+    # (two clock reads) is reported as trials.cold_ms under --full
     eng.sync()
     t0 = time.perf_counter()
     step()
@@ -485,6 +530,48 @@ def main(argv=None):
 
     dt = timed_steps(step, eng.sync, world, args.steps, args.warmup)
     tail = eng.shard_tail()
+    graph_nodes = sorter.graph_nodes()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, last["out"], rank == 0)
+    last.clear()
+
+    sort_s = dt / args.steps
+    sorts = 1 if mode else world  # concurrent sorts in the job
+    value = sorts * N * N * args.steps / dt
+    headline = {
+        "metric": "encrypted rank-sort homomorphic comparisons/s (N^2 per DirectSort<N>::sort)",
+        "value": value,
+        "unit": "cmp/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": sort_s * 1e3,
+        "sort_seconds": sort_s,
+        "higher_is_better": True,
+        "scaling": "strong" if mode else "weak",
+        "vs_baseline": None,
+        "dtype": "u64 (RNS residues, 40/60-bit primes)",
+        "data": "synthetic: seeded permutation of {k/N}, CKKS-encrypted",
+        "config": {"workload": args.workload, "N": N, "ring_dim": 1 << logn, "mult_depth": depth,
+                   "sign": list(cfg), "scale_bits": 40, "secure": secure,
+                   "parallelism": (parallelism(world, groups, mode, tail) if mode
+                                   else f"replicas x{world}")},
+        "graph": {"replayed": graph_nodes > 0, "nodes": graph_nodes,
+                  "note": "timed steps replay the sort as one hipGraph (captured during warmup; "
+                          "SFHE_GRAPH=0 runs them eagerly)"},
+        "full": args.full,
+    }
+    if replicas:
+        headline["replicas"] = replicas
+    if not args.full:  # a plain run ends here
+        if dog:
+            dog.cancel()
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
 
     # profiling leg (after the timed region): one EAGER sort (SFHE_GRAPH=0)
     # with the lanes serialised on one stream and every launch of each family
@@ -493,7 +580,6 @@ def main(argv=None):
     # interval).  Batched ops merge here as in the captured sort (prims.h
     # sfp_batch_*), a merged launch timed as one launch with the bytes of all
     # of its ops; stacked lane regions (SFHE_STACK_BATCHES) are off in both.
-    graph_nodes = sorter.graph_nodes()
     stk0 = eng.stack_stats()
     eng.sync()
     os.environ["SFHE_GRAPH"] = "0"  # per-launch timing needs the eager path
@@ -507,6 +593,7 @@ def main(argv=None):
     step()
     eng.sync()
     serial_ms = (time.perf_counter() - t0) * 1e3
+    last.clear()
     stats = eng.op_stats()  # the SURVEY §8(d) byte model over one (eager) sort
     collectives = None
     if mode:  # each rank's exchange share of a sort, so the 1 -> 8 curve decomposes
@@ -629,31 +716,9 @@ def main(argv=None):
         "timing": timing,
     }
 
-    sort_s = dt / args.steps
-    sorts = 1 if mode else world  # concurrent sorts in the job
-    value = sorts * N * N * args.steps / dt
     result = {
-        "metric": "encrypted rank-sort homomorphic comparisons/s (N^2 per DirectSort<N>::sort)",
-        "value": value,
-        "unit": "cmp/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": sort_s * 1e3,
-        "sort_seconds": sort_s,
-        "higher_is_better": True,
-        "scaling": "strong" if mode else "weak",
-        "vs_baseline": None,
-        "dtype": "u64 (RNS residues, 40/60-bit primes)",
-        "data": "synthetic: seeded permutation of {k/N}, CKKS-encrypted",
-        "config": {"workload": args.workload, "N": N, "ring_dim": 1 << logn, "mult_depth": depth,
-                   "sign": list(cfg), "scale_bits": 40, "secure": secure,
-                   "parallelism": (parallelism(world, groups, mode, tail) if mode
-                                   else f"replicas x{world}")},
+        **headline,
         "algorithmic_gb_per_sort": stats["algo_bytes"] / 1e9,
-        "graph": {"replayed": graph_nodes > 0, "nodes": graph_nodes,
-                  "note": "timed steps replay the sort as one hipGraph (captured during warmup; "
-                          "SFHE_GRAPH=0 runs them eagerly)"},
         # the sort's algorithmic bytes over the timed sort's wall time, against HBM peak
         "whole_sort_frac": stats["algo_bytes"] / sort_s / (HBM_PEAK_GBS * 1e9),
         "batched_ops": {"merged_launches_per_sort": stk1[0] - stk0[0],
@@ -675,8 +740,6 @@ def main(argv=None):
     }
     if collectives:
         result["collectives"] = collectives
-    if replicas:
-        result["replicas"] = replicas
     if dog:
         dog.cancel()
     def leg(name):  # progress on stderr (a crash inside a leg names it)

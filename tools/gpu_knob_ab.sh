@@ -7,7 +7,7 @@ set -o pipefail
 T=${1:-r05k}
 mkdir -p gpurun_out/$T
 export PYTHONUNBUFFERED=1
-B="--no-kway --no-hybrid1 --no-c5 --no-cpu-baseline --trials 1 --steps 20 --warmup 3"
+B="--full --no-kway --no-hybrid1 --no-c5 --no-cpu-baseline --trials 1 --steps 20 --warmup 3"
 for k in 1 2; do
   timeout -k 10 300 python -u bench.py $B > gpurun_out/$T/default_$k.json 2>/dev/null || exit 1
   for v in 64 256; do

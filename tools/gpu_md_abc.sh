@@ -10,7 +10,7 @@ export PYTHONUNBUFFERED=1
 timeout -k 10 400 python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu \
     tests/test_gpu_parity_metric.py tests/test_gpu_parity_sort.py \
     > gpurun_out/$T/gpu_tests.log 2>&1 || exit $?
-B="--no-kway --no-hybrid1 --no-c5 --no-cpu-baseline --trials 1 --steps 20 --warmup 3"
+B="--full --no-kway --no-hybrid1 --no-c5 --no-cpu-baseline --trials 1 --steps 20 --warmup 3"
 L2=$PWD/sorting-fhe_amd/build_md2/libsfhe.so
 for k in 1 2; do
   SFHE_MODDOWN_COL=0 timeout -k 10 300 python -u bench.py $B > gpurun_out/$T/unfused_$k.json 2>/dev/null || exit 1

@@ -15,5 +15,5 @@ SFHE_LAZY=0 timeout -k 10 200 $P ds 256 16 0 > ${O}_ds16_nolazy.log 2>&1 || exit
 timeout -k 10 200 $P ds 256 17 1 > ${O}_ds17.log 2>&1 || exit 1
 timeout -k 10 200 $P h 256 17 1 > ${O}_h.log 2>&1 || exit 1
 timeout -k 10 200 $P h2 256 17 1 > ${O}_h2.log 2>&1 || exit 1
-timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-kway --no-c5 --no-cpu-baseline --trials 3 > ${O}_bench.log 2>&1 || exit 1
-SFHE_LAZY=0 timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-kway --no-c5 --no-cpu-baseline --no-hybrid1 --trials 3 > ${O}_bench_nolazy.log 2>&1
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-kway --no-c5 --no-cpu-baseline --trials 3 > ${O}_bench.log 2>&1 || exit 1
+SFHE_LAZY=0 timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-kway --no-c5 --no-cpu-baseline --no-hybrid1 --trials 3 > ${O}_bench_nolazy.log 2>&1

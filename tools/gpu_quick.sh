@@ -9,8 +9,8 @@ timeout -k 10 600 python -u -m pytest -x -v -s --timeout 300 --timeout-method th
     tests/test_gpu_parity.py tests/test_fusion.py tests/test_gpu_graph.py tests/test_shard.py \
     "tests/test_gpu_sort.py::test_precision_attribution" "tests/test_serialization.py::test_fherma_flow_config_json" \
     > ${O}_tests.log 2>&1 || exit 1
-timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-kway --no-c5 --no-cpu-baseline --trials 3 > ${O}_bench.log 2>&1 || exit 1
-SFHE_LAZY=0 timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-kway --no-c5 --no-cpu-baseline --no-hybrid1 --trials 3 > ${O}_bench_nolazy.log 2>&1
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-kway --no-c5 --no-cpu-baseline --trials 3 > ${O}_bench.log 2>&1 || exit 1
+SFHE_LAZY=0 timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-kway --no-c5 --no-cpu-baseline --no-hybrid1 --trials 3 > ${O}_bench_nolazy.log 2>&1
 [ -n "$C5PROF" ] || exit 0
 # the config-5 sort (2^17) under the kernel trace, eagerly launched: replaying
 # its captured graph under rocprofv3 segfaults inside the profiler

@@ -9,14 +9,15 @@ set -o pipefail
 cd "$(dirname "$0")/.."
 export PYTHONUNBUFFERED=1
 T=${TAG:-r05x}
-mkdir -p gpurun_out
+O=${SFHE_OUT:-bench_out}
+mkdir -p $O
 if [ -n "$TESTS" ]; then
     [ "$TESTS" = all ] && TESTS=tests
     timeout -k 10 ${TESTS_LIMIT:-1000} python -u -m pytest -x -v --timeout 900 --timeout-method thread --durations=15 \
-        $TESTS -m gpu > gpurun_out/${T}_gpu_tests.log 2>&1 || exit $?
+        $TESTS -m gpu > $O/${T}_gpu_tests.log 2>&1 || exit $?
 fi
 if [ -n "$BENCH" ]; then
-    timeout -k 10 600 python -u bench.py $BENCHARGS > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || exit $?
+    timeout -k 10 600 python -u bench.py --full $BENCHARGS > $O/${T}_bench.json 2> $O/${T}_bench.err || exit $?
 fi
 if [ -n "$PROFILE" ]; then
     bash tools/profile_round.sh "$T" || exit $?

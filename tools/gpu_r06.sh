@@ -24,7 +24,7 @@ if [ -n "$CHAIN" ]; then
     done
 fi
 if [ -n "$BENCH" ]; then
-    B=${BENCHARGS:-"--steps 10 --warmup 3 --no-kway --no-cpu-baseline --no-hybrid1 --no-c5 --trials 3"}
+    B="--full "${BENCHARGS:-"--steps 10 --warmup 3 --no-kway --no-cpu-baseline --no-hybrid1 --no-c5 --trials 3"}
     for r in $(seq 1 ${REPS:-1}); do
         timeout -k 10 400 python -u bench.py $B > $O/bench$r.json 2> $O/bench$r.err || exit $?
         for ab in $AB; do  # (one setting per word; '+' joins several)

@@ -14,7 +14,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
     tests/test_gpu_stack.py tests/test_gpu_parity_sort.py::test_metric_sort_bitexact tests/test_gpu_graph.py \
     tests/test_hybrid_variants.py tests/test_gpu_shard.py tests/test_gpu_multigpu.py -m gpu > gpurun_out/${T}_tests.log 2>&1 || exit $?
 fi
-B="--no-kway --no-hybrid1 --no-c5 --no-cpu-baseline --trials 5 --steps 20 --warmup 3"
+B="--full --no-kway --no-hybrid1 --no-c5 --no-cpu-baseline --trials 5 --steps 20 --warmup 3"
 for k in 1 2; do
     timeout -k 10 300 python -u bench.py $B > gpurun_out/${T}_A_$k.json 2> gpurun_out/${T}_A_$k.err || exit $?
     SFHE_STACK_BATCHES=0 timeout -k 10 300 python -u bench.py $B > gpurun_out/${T}_B_$k.json 2> gpurun_out/${T}_B_$k.err || exit $?

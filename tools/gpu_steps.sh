@@ -22,7 +22,7 @@ if [ "${TESTS:-}" != "none" ]; then
     ok $? tests
 fi
 if [ "${BENCH_ARGS:-none}" != "none" ]; then
-    timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py ${BENCH_ARGS} > ${O}_bench.log 2>&1
+    timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py --full ${BENCH_ARGS} > ${O}_bench.log 2>&1
     ok $? bench
 fi
 exit 0

@@ -12,7 +12,7 @@ timeout -k 10 700 python -u -m pytest -x -v --timeout 400 --timeout-method threa
     tests/test_gpu_stack.py tests/test_hybrid_variants.py tests/test_kway.py tests/test_gpu_sort.py -m gpu \
     > gpurun_out/${T}_tests.log 2>&1 || exit $?
 fi
-B="--no-kway --no-hybrid1 --no-c5 --no-cpu-baseline --trials 3 --steps 20 --warmup 3"
+B="--full --no-kway --no-hybrid1 --no-c5 --no-cpu-baseline --trials 3 --steps 20 --warmup 3"
 for k in 1 2; do
     timeout -k 10 300 python -u bench.py $B > gpurun_out/${T}_on_$k.json 2> gpurun_out/${T}_on_$k.err || exit $?
     env ${BENV:-SFHE_PS_WAVES=0} timeout -k 10 300 python -u bench.py $B > gpurun_out/${T}_off_$k.json 2> gpurun_out/${T}_off_$k.err || exit $?
