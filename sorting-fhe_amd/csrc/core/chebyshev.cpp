@@ -66,6 +66,7 @@ std::vector<double> EvalChebyshevCoefficients(std::function<double(double)> func
 namespace {
 
 using Ct = Ciphertext<DCRTPoly>;
+using Addend = CryptoContextImpl<DCRTPoly>::MultAddend;
 
 struct Val {
     bool isConst = true;
@@ -105,6 +106,24 @@ class PSEvaluator {
                 as.push_back(doubled(j / 2));
                 bs.push_back(j % 2 == 0 ? T[j / 2] : T[j / 2 + 1]);
             }
+            uint32_t top = 0;  // the wave's deepest product level
+            for (size_t i = 0; i < as.size(); ++i) top = std::max(top, std::max(as[i]->GetLevel(), bs[i]->GetLevel()) + 1);
+            if (psFma() && top <= cc->GetMultiplicativeDepth()) {  // (past the chain's end the products below throw)
+                // the "- 1" / "- T_1" of each step in its product's last pass
+                // (EvalMultAdd: the same values; T_1 aligned before the wave)
+                std::vector<Addend> adds;
+                for (uint32_t j = lo; j <= hi; ++j) {
+                    const uint32_t lv = std::max(as[j - lo]->GetLevel(), bs[j - lo]->GetLevel()) + 1;
+                    adds.push_back(j % 2 == 0 ? Addend{nullptr, 1, -1.0} : Addend{atLevel(1, lv), -1, 0.0});
+                }
+                if (psWaves()) {
+                    auto ts = cc->EvalMultManyAdd(as, bs, adds);
+                    for (uint32_t j = lo; j <= hi; ++j) T[j] = ts[j - lo];
+                } else {
+                    for (uint32_t j = lo; j <= hi; ++j) T[j] = cc->EvalMultAdd(as[j - lo], bs[j - lo], adds[j - lo]);
+                }
+                continue;
+            }
             std::vector<Ct> prods;
             if (psWaves()) {
                 prods = cc->EvalMultMany(as, bs);
@@ -128,6 +147,7 @@ class PSEvaluator {
         std::map<uint32_t, std::vector<size_t>> byLevel;
         for (size_t i = 0; i < leaves.size(); ++i) byLevel[leaves[i].second].push_back(i);
         pre.assign(leaves.size(), nullptr);
+        preConst.assign(leaves.size(), 0);
         for (auto& kv : byLevel) {
             const uint32_t L = kv.first;
             std::vector<uint32_t> js;  // inputs used by any leaf of this level
@@ -150,15 +170,21 @@ class PSEvaluator {
             }
             for (size_t b0 = 0; b0 < kv.second.size(); b0 += 64) {
                 std::vector<std::vector<double>> w;
+                std::vector<double> c0;  // the leaves' constant terms: into the rescale's last pass
                 const size_t b1 = std::min(kv.second.size(), b0 + 64);
                 for (size_t t = b0; t < b1; ++t) {
                     const auto& pl = leaves[kv.second[t]].first;
                     std::vector<double> row;
                     for (uint32_t j : js) row.push_back(j < pl.size() ? pl[j] : 0.0);
                     w.push_back(std::move(row));
+                    c0.push_back(pl[0]);
                 }
-                auto cts = cc->LinearWSumRescaleMulti(ins0, ins1, w, L, T[1]->GetSlots(), &sc);
-                for (size_t t = b0; t < b1; ++t) pre[kv.second[t]] = cts[t - b0];
+                bool added = false;
+                auto cts = cc->LinearWSumRescaleMulti(ins0, ins1, w, L, T[1]->GetSlots(), &sc, &c0, &added);
+                for (size_t t = b0; t < b1; ++t) {
+                    pre[kv.second[t]] = cts[t - b0];
+                    preConst[kv.second[t]] = added;
+                }
             }
         }
         nextLeaf = 0;
@@ -193,18 +219,27 @@ class PSEvaluator {
         if (half) cc->SetLane(lane + half);
         Val qv = eval(q, depth - 1, Lp - 1, half ? lane + half : lane, half ? half : 1);
         const Ct& TM = alignedPower(M, Lp - 1);
-        Val out;
+        // one lane and a ciphertext quotient: r first, so the sum rides in the
+        // product's last pass (EvalMultAdd: the same values)
+        const bool fold = !half && psFma() && !qv.isConst;
+        Val out, rv;
         out.isConst = false;
-        if (qv.isConst)
-            out.ct = cc->EvalMult(TM, qv.c);
-        else
-            out.ct = cc->EvalMult(qv.ct, TM);
-        if (half) cc->SetLane(lane);
-        Val rv = eval(r, depth, Lp, lane, half ? half : 1);
+        if (fold) {
+            rv = eval(r, depth, Lp, lane, 1);
+            out.ct = cc->EvalMultAdd(qv.ct, TM, rv.isConst ? Addend{nullptr, 1, rv.c} : Addend{rv.ct, 1, 0.0});
+        } else {
+            if (qv.isConst)
+                out.ct = cc->EvalMult(TM, qv.c);
+            else
+                out.ct = cc->EvalMult(qv.ct, TM);
+            if (half) cc->SetLane(lane);
+            rv = eval(r, depth, Lp, lane, half ? half : 1);
+        }
         if (std::getenv("SFHE_PS_DEBUG"))
             std::fprintf(stderr, "PSNODE deg %u M %u | q %s lvl %d | TM lvl %u | prod lvl %u | r %s lvl %d\n", deg, M,
                          qv.isConst ? "const" : "ct", qv.isConst ? -1 : (int)qv.ct->GetLevel(), TM->GetLevel(),
                          out.ct->GetLevel(), rv.isConst ? "const" : "ct", rv.isConst ? -1 : (int)rv.ct->GetLevel());
+        if (fold) return out;
         if (rv.isConst) {
             if (rv.c != 0.0) out.ct = cc->EvalAdd(out.ct, rv.c);
         } else {
@@ -258,7 +293,9 @@ class PSEvaluator {
             for (auto& w : waves) {
                 const Ct& TM = alignedPower(w.first.first, w.first.second - 1);
                 std::vector<Ct> as, bs;
+                std::vector<Addend> adds;  // a node whose r is ready now: its sum in the product's last pass
                 std::vector<size_t> which;
+                bool anyAdd = false;
                 for (size_t i : w.second) {
                     Node& nd = nodes[i];
                     if (nd.q.isConst) {
@@ -269,11 +306,21 @@ class PSEvaluator {
                     as.push_back(value(nd.q));
                     bs.push_back(TM);
                     which.push_back(i);
+                    const bool fold = psFma() && ready(nd.r);  // (never waited for: the product goes now)
+                    adds.push_back(!fold ? Addend{} : nd.r.isConst ? Addend{nullptr, 1, nd.r.c} : Addend{value(nd.r), 1, 0.0});
+                    nd.sumInProd = fold;
+                    anyAdd = anyAdd || fold;
                 }
-                auto prods = cc->EvalMultMany(as, bs);
+                auto prods = anyAdd ? cc->EvalMultManyAdd(as, bs, adds) : cc->EvalMultMany(as, bs);
                 for (size_t t = 0; t < which.size(); ++t) {
-                    nodes[which[t]].prod = prods[t];
-                    nodes[which[t]].hasProd = true;
+                    Node& nd = nodes[which[t]];
+                    nd.hasProd = true;
+                    if (nd.sumInProd) {
+                        nd.out = prods[t];
+                        nd.hasOut = true;
+                    } else {
+                        nd.prod = prods[t];
+                    }
                 }
                 progress = true;
             }
@@ -310,7 +357,7 @@ class PSEvaluator {
         Val q, r;
         uint32_t M = 0, Lp = 0;
         Ct prod, out;
-        bool hasProd = false, hasOut = false;
+        bool hasProd = false, hasOut = false, sumInProd = false;
     };
     std::vector<Node> nodes;
 
@@ -415,7 +462,7 @@ class PSEvaluator {
         if (it != giant.end()) return it->second;
         const Ct& half = power(M / 2);
         const Ct twice = cc->EvalAdd(half, half);  // 2 T_M before the rescale, as above
-        return giant[i] = cc->EvalAdd(cc->EvalMult(twice, half), -1.0);
+        return giant[i] = cc->EvalMultAdd(twice, half, Addend{nullptr, 1, -1.0});
     }
 
     // 2 T_j, memoised (an odd T_j+1's product reuses T_j's)
@@ -451,8 +498,9 @@ class PSEvaluator {
             Val out;
             out.isConst = false;
             out.ct = pre[nextLeaf];
+            const bool constIn = preConst[nextLeaf];
             pre[nextLeaf++] = nullptr;
-            if (p[0] != 0.0) out.ct = cc->EvalAdd(out.ct, p[0]);
+            if (p[0] != 0.0 && !constIn) out.ct = cc->EvalAdd(out.ct, p[0]);
             return out;
         }
         const int lv = leafSumLevel(p, want);
@@ -472,20 +520,30 @@ class PSEvaluator {
         }
         Val out;
         out.isConst = false;
-        out.ct = cc->LinearWSumRescale(ins0, ins1, w, (uint32_t)lv, T[1]->GetSlots(), &sc);
-        if (p[0] != 0.0) out.ct = cc->EvalAdd(out.ct, p[0]);
+        out.ct = cc->LinearWSumRescale(ins0, ins1, w, (uint32_t)lv, T[1]->GetSlots(), &sc, p[0]);
         return out;
     }
 
     CryptoContextImpl<DCRTPoly>* cc;
     uint32_t l, k, D;
     std::vector<Ct> pre;  // precomputed leaves in visiting order
+    std::vector<char> preConst;  // ... whose constant term the rescale already added
     size_t nextLeaf = 0;
     std::vector<Ct> T;
     std::map<uint32_t, Ct> giant;
     std::map<std::pair<uint32_t, uint32_t>, Ct> aligned, alignedPow;
     std::map<uint32_t, Ct> twice;
 };
+
+// SFHE_PS_DEBUG: the context's running counts of sums folded into a producing
+// op's last pass (a silent fall-back to the separate ops shows as no change)
+void psDebugCounts(const CryptoContextImpl<DCRTPoly>* cc, const char* where) {
+    if (!std::getenv("SFHE_PS_DEBUG")) return;
+    uint64_t sums = 0, consts = 0, pairs = 0;
+    cc->FusedSumCounts(&sums, &consts, &pairs);
+    std::fprintf(stderr, "PSFMA %s | fused sums %llu | fused constants %llu | paired weighted sums %llu\n", where,
+                 (unsigned long long)sums, (unsigned long long)consts, (unsigned long long)pairs);
+}
 
 }  // namespace
 
@@ -578,6 +636,7 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalChebyshevSeriesPS(
     if (out->GetLevel() > target)
         SFHE_THROW("internal: Chebyshev evaluation exceeded OpenFHE depth");
     if (out->GetLevel() < target) out = AdjustLevel(out, target);
+    psDebugCounts(this, "EvalChebyshevSeriesPS");
     return out;
 }
 
@@ -640,8 +699,8 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalPolyLinear(
         w.push_back(p[j]);
         sc.push_back(pw[j]->scale);
     }
-    auto out = LinearWSumRescale(i0, i1, w, lev, x->GetSlots(), &sc);
-    if (p[0] != 0.0) out = EvalAdd(out, p[0]);
+    auto out = LinearWSumRescale(i0, i1, w, lev, x->GetSlots(), &sc, p[0]);  // (+ p[0]: in the rescale's last pass)
+    psDebugCounts(this, "EvalPolyLinear");
     return out;
 }
 

@@ -495,8 +495,10 @@ class SfheInternal {
     }
 
     // (c0,c1) at level l, ell limbs, any scale -> new ct at level l+1
+    // cst (2 * rows(ell - 1) residues: c0's, then zeros) is added in the
+    // rescale's last pass where the backend has that form: *cstDone = true
     static Ct rescale(CC* cc, const uint64_t* c0, const uint64_t* c1, uint32_t level,
-                      uint32_t slots) {
+                      uint32_t slots, const uint64_t* cst = nullptr, bool* cstDone = nullptr) {
         SfheContextState* s = cc->st.get();
         uint32_t ell = s->ellOf(level);
         if (ell < 2) SFHE_THROW("no levels left to rescale (multiplicative depth exhausted)");
@@ -504,6 +506,10 @@ class SfheInternal {
         if (c1 - c0 < 0) SFHE_THROW("internal: layout");
         if (s->shardAt(ell))
             rescaleShard(s, out->c0, c0, ell, 2, (size_t)(c1 - c0), (size_t)(out->c1 - out->c0));
+        else if (cst && sfp_rescale_add &&
+                 sfp_rescale_add(s->dev, out->c0, c0, ell, s->qInvTable[ell].data(), 2, (size_t)(c1 - c0),
+                                 (size_t)(out->c1 - out->c0), cst) == 0)
+            *cstDone = true;
         else
             sfp_rescale(s->dev, out->c0, c0, ell, s->qInvTable[ell].data(), 2, (size_t)(c1 - c0),
                         (size_t)(out->c1 - out->c0));
@@ -969,11 +975,38 @@ class SfheInternal {
         s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
     }
 
+    // A sum for the last pass of a product's rescale (prims.h sfp_*_add):
+    // rows of a canonical ciphertext at the output level, added or
+    // subtracted, and / or per-row constants for c0.  done: the backend took it.
+    struct Fma {
+        const uint64_t *r0 = nullptr, *r1 = nullptr;
+        int sign = 1;
+        const uint64_t* cst = nullptr;
+        bool done = false;
+        explicit operator bool() const { return r0 || cst; }
+    };
+
+    // a sum the backend took: counted as the EvalAdd it replaces (the byte
+    // model is algorithmic), and in the fused-op counters
+    static void countFused(SfheContextState* s, const CC::MultAddend& add, uint32_t ell) {
+        if (add.r) {
+            s->fusedSums++;
+            s->stats.add++;
+            s->countBytes(6.0 * ell * s->n * 8);
+        }
+        if (add.c != 0.0) {
+            s->fusedConsts++;
+            s->stats.add++;
+            s->countBytes(4.0 * ell * s->n * 8);
+        }
+    }
+
     // EvalMult's tail: relinearise (d0, d1, d2) at `level` and rescale, with the
     // ModDown and the rescale fused (sfp_moddown_rescale): the same result as
     // keySwitch(d2, +d0, +d1) followed by rescale(), four launches fewer.
+    // f: a sum for its last pass, taken where the backend has that form.
     static Ct relinRescale(CC* cc, uint64_t* d0, uint64_t* d1, const uint64_t* d2, uint32_t level,
-                           uint32_t slots) {
+                           uint32_t slots, Fma* f = nullptr) {
         SfheContextState* s = cc->st.get();
         const uint32_t ell = s->ellOf(level);
         if (ell < 2) SFHE_THROW("no levels left to rescale (multiplicative depth exhausted)");
@@ -990,9 +1023,16 @@ class SfheInternal {
         const int rowDone = modupInner(cc, acc->ptr, d2, ell, key, d0, d1, s->pModQof(tier)[ell - 1], 0, ell - 1);
         Ct out = newCt(cc, level + 1, slots);
         auto scratch = s->alloc((size_t)2 * (ell - 1) * n);
-        sfp_moddown_rescale(s->dev, out->c0, out->c1, d0, d1, acc->ptr, stride, ell, K, s->Lq,
-                            s->moddownConvOf(tier), s->pInvModQof(tier), s->pModQof(tier),
-                            s->qInvTable[ell].data(), scratch->ptr, rowDone);
+        if (f && *f && sfp_moddown_rescale_add &&
+            sfp_moddown_rescale_add(s->dev, out->c0, out->c1, d0, d1, acc->ptr, stride, ell, K, s->Lq,
+                                    s->moddownConvOf(tier), s->pInvModQof(tier), s->pModQof(tier),
+                                    s->qInvTable[ell].data(), scratch->ptr, rowDone, f->r0, f->r1, f->sign,
+                                    f->cst) == 0)
+            f->done = true;
+        else
+            sfp_moddown_rescale(s->dev, out->c0, out->c1, d0, d1, acc->ptr, stride, ell, K, s->Lq,
+                                s->moddownConvOf(tier), s->pInvModQof(tier), s->pModQof(tier),
+                                s->qInvTable[ell].data(), scratch->ptr, rowDone);
         s->stats.keyswitch++;
         s->stats.rescale++;
         s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
@@ -1005,7 +1045,7 @@ class SfheInternal {
     // has it (sfp_mult_relin_rescale: the tensor is formed inside the key
     // switch's passes, never written out), else the tensor then relinRescale.
     static Ct multRelinRescale(CC* cc, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0,
-                               const uint64_t* b1, uint32_t level, uint32_t slots) {
+                               const uint64_t* b1, uint32_t level, uint32_t slots, Fma* f = nullptr) {
         SfheContextState* s = cc->st.get();
         const uint32_t ell = s->ellOf(level);
         if (ell < 2) SFHE_THROW("no levels left to rescale (multiplicative depth exhausted)");
@@ -1020,10 +1060,20 @@ class SfheInternal {
             auto ext = s->alloc(stride * beta);
             auto scratch = s->alloc((size_t)2 * ell * n);
             auto& convs = modupConv(cc, ell, tier);
-            if (sfp_mult_relin_rescale(s->dev, out->c0, out->c1, a0, a1, b0, b1, ell, K, s->Lq, s->alpha,
-                                       convs.data(), key->ptr, s->moddownConvOf(tier), s->pInvModQof(tier),
-                                       s->pModQof(tier), s->qInvTable[ell].data(), acc->ptr, ext->ptr,
-                                       scratch->ptr) == 0) {
+            int rc = -1;
+            if (f && *f && sfp_mult_relin_rescale_add) {
+                rc = sfp_mult_relin_rescale_add(s->dev, out->c0, out->c1, a0, a1, b0, b1, ell, K, s->Lq, s->alpha,
+                                                convs.data(), key->ptr, s->moddownConvOf(tier),
+                                                s->pInvModQof(tier), s->pModQof(tier), s->qInvTable[ell].data(),
+                                                acc->ptr, ext->ptr, scratch->ptr, f->r0, f->r1, f->sign, f->cst);
+                if (rc == 0) f->done = true;
+            }
+            if (rc != 0)
+                rc = sfp_mult_relin_rescale(s->dev, out->c0, out->c1, a0, a1, b0, b1, ell, K, s->Lq, s->alpha,
+                                            convs.data(), key->ptr, s->moddownConvOf(tier), s->pInvModQof(tier),
+                                            s->pModQof(tier), s->qInvTable[ell].data(), acc->ptr, ext->ptr,
+                                            scratch->ptr);
+            if (rc == 0) {
                 s->stats.keyswitch++;
                 s->stats.rescale++;
                 s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
@@ -1036,7 +1086,7 @@ class SfheInternal {
         uint64_t* d1 = d0 + pw;
         uint64_t* d2 = d1 + pw;
         sfp_tensor(s->dev, d0, d1, d2, a0, a1, b0, b1, s->qmap(ell));
-        return relinRescale(cc, d0, d1, d2, level, slots);
+        return relinRescale(cc, d0, d1, d2, level, slots, f);
     }
 
     // multRelinRescale of up to SFP_BATCH_MAX independent operand pairs at one
@@ -1046,7 +1096,7 @@ class SfheInternal {
     // cannot fuse run one by one (multRelinRescale: the same values).
     static std::vector<Ct> multRelinRescaleMany(CC* cc, const std::vector<const CiphertextImpl<DCRTPoly>*>& a,
                                                 const std::vector<const CiphertextImpl<DCRTPoly>*>& b, uint32_t level,
-                                                const std::vector<uint32_t>& slots) {
+                                                const std::vector<uint32_t>& slots, std::vector<Fma>* fs = nullptr) {
         SfheContextState* s = cc->st.get();
         const size_t cnt = a.size();
         const uint32_t ell = s->ellOf(level);
@@ -1067,11 +1117,23 @@ class SfheInternal {
                 auto ext = s->alloc(stride * beta);
                 auto scratch = s->alloc((size_t)2 * ell * n);
                 bs.lane((uint32_t)done);
-                if (sfp_mult_relin_rescale(s->dev, out[done]->c0, out[done]->c1, a[done]->c0, a[done]->c1,
-                                           b[done]->c0, b[done]->c1, ell, K, s->Lq, s->alpha, convs.data(),
-                                           key->ptr, s->moddownConvOf(tier), s->pInvModQof(tier), s->pModQof(tier),
-                                           s->qInvTable[ell].data(), acc->ptr, ext->ptr, scratch->ptr) != 0)
-                    break;  // (no fused form: nothing issued for this pair)
+                Fma* f = fs && (*fs)[done] ? &(*fs)[done] : nullptr;
+                int rc = -1;
+                if (f && sfp_mult_relin_rescale_add) {
+                    rc = sfp_mult_relin_rescale_add(s->dev, out[done]->c0, out[done]->c1, a[done]->c0, a[done]->c1,
+                                                    b[done]->c0, b[done]->c1, ell, K, s->Lq, s->alpha, convs.data(),
+                                                    key->ptr, s->moddownConvOf(tier), s->pInvModQof(tier),
+                                                    s->pModQof(tier), s->qInvTable[ell].data(), acc->ptr, ext->ptr,
+                                                    scratch->ptr, f->r0, f->r1, f->sign, f->cst);
+                    if (rc == 0) f->done = true;
+                }
+                if (rc != 0)
+                    rc = sfp_mult_relin_rescale(s->dev, out[done]->c0, out[done]->c1, a[done]->c0, a[done]->c1,
+                                                b[done]->c0, b[done]->c1, ell, K, s->Lq, s->alpha, convs.data(),
+                                                key->ptr, s->moddownConvOf(tier), s->pInvModQof(tier),
+                                                s->pModQof(tier), s->qInvTable[ell].data(), acc->ptr, ext->ptr,
+                                                scratch->ptr);
+                if (rc != 0) break;  // (no fused form: nothing issued for this pair)
                 s->stats.keyswitch++;
                 s->stats.rescale++;
                 s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
@@ -1080,7 +1142,8 @@ class SfheInternal {
         }
         }
         for (size_t i = done; i < cnt; ++i)
-            out[i] = multRelinRescale(cc, a[i]->c0, a[i]->c1, b[i]->c0, b[i]->c1, level, slots[i]);
+            out[i] = multRelinRescale(cc, a[i]->c0, a[i]->c1, b[i]->c0, b[i]->c1, level, slots[i],
+                                      fs ? &(*fs)[i] : nullptr);
         return out;
     }
 
@@ -2841,6 +2904,135 @@ std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultMany(
     return out;
 }
 
+// ---- a product with the sum that follows it (the polynomial evaluators) ----
+namespace {
+// prod (+|-) r (+ c) as today's separate ops
+Ciphertext<DCRTPoly> addAfter(CryptoContextImpl<DCRTPoly>* cc, Ciphertext<DCRTPoly> prod,
+                              const CryptoContextImpl<DCRTPoly>::MultAddend& add) {
+    if (add.r) prod = add.sign < 0 ? cc->EvalSub(prod, add.r) : cc->EvalAdd(prod, add.r);
+    if (add.c != 0.0) prod = cc->EvalAdd(prod, add.c);
+    return prod;
+}
+}  // namespace
+
+// Can `add` ride in the last pass of the product of a and b (the conditions
+// of EvalMultAdd, openfhe.h)?
+bool CryptoContextImpl<DCRTPoly>::multAddFusable(const Ciphertext<DCRTPoly>& a, const Ciphertext<DCRTPoly>& b,
+                                                 const MultAddend& add) const {
+    SfheContextState* s = st.get();
+    if (!psFma() || !SfheInternal::fusedRescale() || SfheInternal::lazy(s) || !s->relinKey) return false;
+    if (!add.r && add.c == 0.0) return false;
+    if (SfheInternal::isLazy(a) || SfheInternal::isLazy(b)) return false;
+    const uint32_t level = std::max(a->level, b->level);
+    const uint32_t ell = s->ellOf(level);
+    if (ell < 2 || s->shardAt(ell) || level + 1 > s->L) return false;
+    if (add.r) {
+        const auto& r = add.r;
+        if (SfheInternal::isLazy(r) || r->level != level + 1 || r->scale != s->scale[level + 1] ||
+            r->c1 - r->c0 != (ptrdiff_t)s->polyWords(level + 1))
+            return false;
+    }
+    return true;
+}
+
+Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMultAdd(const Ciphertext<DCRTPoly>& a0,
+                                                             const Ciphertext<DCRTPoly>& b0,
+                                                             const MultAddend& add) {
+    OpLock g(st.get());
+    if (!multAddFusable(a0, b0, add)) return addAfter(this, EvalMult(a0, b0), add);
+    SfheContextState* s = st.get();
+    SfheInternal::deps(s, {&a0, &b0, &add.r});
+    auto a = a0, b = b0;
+    SfheInternal::align(this, a, b);
+    const uint32_t ell = s->ellOf(a->level), slots = std::max(a->slots, b->slots);
+    s->stats.tensor++;
+    s->countBytes(7.0 * ell * s->n * 8);
+    std::vector<uint64_t> k;
+    SfheInternal::Fma f;
+    if (add.r) {
+        f.r0 = add.r->c0;
+        f.r1 = add.r->c1;
+        f.sign = add.sign;
+    }
+    if (add.c != 0.0) {
+        k = SfheInternal::constResidues(s, add.c * s->scale[a->level + 1], ell - 1);
+        f.cst = k.data();
+    }
+    auto out = SfheInternal::traced(
+        this, SfheInternal::multRelinRescale(this, a->c0, a->c1, b->c0, b->c1, a->level, slots, &f), "EvalMult");
+    if (!f.done) return addAfter(this, out, add);
+    SfheInternal::countFused(s, add, ell - 1);
+    return out;
+}
+
+std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultManyAdd(
+    const std::vector<Ciphertext<DCRTPoly>>& a0, const std::vector<Ciphertext<DCRTPoly>>& b0,
+    const std::vector<MultAddend>& adds) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    if (a0.size() != b0.size() || a0.size() != adds.size()) SFHE_THROW("operand count mismatch");
+    const size_t cnt = a0.size();
+    std::vector<Ciphertext<DCRTPoly>> out(cnt);
+    if (cnt < 2) {
+        for (size_t i = 0; i < cnt; ++i) out[i] = EvalMultAdd(a0[i], b0[i], adds[i]);
+        return out;
+    }
+    if (!psFma() || !SfheInternal::fusedRescale() || SfheInternal::lazy(s)) {
+        // nothing can be folded: the batched products as EvalMultMany forms them, then the sums
+        out = EvalMultMany(a0, b0);
+        for (size_t i = 0; i < cnt; ++i) out[i] = addAfter(this, out[i], adds[i]);
+        return out;
+    }
+    if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalMult");
+    std::vector<Ciphertext<DCRTPoly>> A(a0), B(b0);
+    std::vector<char> fuse(cnt);
+    for (size_t i = 0; i < cnt; ++i) {
+        fuse[i] = multAddFusable(a0[i], b0[i], adds[i]);
+        SfheInternal::deps(s, {&a0[i], &b0[i]});
+        if (fuse[i]) SfheInternal::deps(s, {&adds[i].r});
+        SfheInternal::align(this, A[i], B[i]);
+        if (s->ellOf(A[i]->level) < 2) SFHE_THROW("no levels left (multiplicative depth exhausted)");
+        s->stats.tensor++;
+        s->countBytes(7.0 * s->ellOf(A[i]->level) * s->n * 8);
+    }
+    // runs of up to SFP_BATCH_MAX consecutive pairs at one level (EvalMultMany)
+    for (size_t i = 0; i < cnt;) {
+        size_t j = i + 1;
+        while (j < cnt && j - i < batchWidth() && A[j]->level == A[i]->level) ++j;
+        const uint32_t level = A[i]->level, ell = s->ellOf(level);
+        std::vector<const CiphertextImpl<DCRTPoly>*> pa, pb;
+        std::vector<uint32_t> slots;
+        std::vector<SfheInternal::Fma> fs(j - i);
+        std::vector<std::vector<uint64_t>> ks(j - i);
+        for (size_t k = i; k < j; ++k) {
+            pa.push_back(A[k].get());
+            pb.push_back(B[k].get());
+            slots.push_back(std::max(A[k]->slots, B[k]->slots));
+            if (!fuse[k]) continue;
+            SfheInternal::Fma& f = fs[k - i];
+            if (adds[k].r) {
+                f.r0 = adds[k].r->c0;
+                f.r1 = adds[k].r->c1;
+                f.sign = adds[k].sign;
+            }
+            if (adds[k].c != 0.0) {
+                ks[k - i] = SfheInternal::constResidues(s, adds[k].c * s->scale[level + 1], ell - 1);
+                f.cst = ks[k - i].data();
+            }
+        }
+        auto r = SfheInternal::multRelinRescaleMany(this, pa, pb, level, slots, &fs);
+        for (size_t k = i; k < j; ++k) {
+            out[k] = SfheInternal::traced(this, r[k - i], "EvalMult");
+            if (fs[k - i].done)
+                SfheInternal::countFused(s, adds[k], ell - 1);
+            else
+                out[k] = addAfter(this, out[k], adds[k]);
+        }
+        i = j;
+    }
+    return out;
+}
+
 Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMultAddPlain(
     const std::vector<Ciphertext<DCRTPoly>>& a, const std::vector<Plaintext>& p) {
     OpLock g(st.get());
@@ -3308,9 +3500,25 @@ void weightResidues(const SfheContextState* s, double w, uint32_t level, uint32_
 std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::LinearWSumRescaleMulti(
     const std::vector<const uint64_t*>& in0, const std::vector<const uint64_t*>& in1,
     const std::vector<std::vector<double>>& w, uint32_t level, uint32_t slots, const std::vector<double>* inScale) {
+    return LinearWSumRescaleMulti(in0, in1, w, level, slots, inScale, nullptr, nullptr);
+}
+
+void CryptoContextImpl<DCRTPoly>::FusedSumCounts(uint64_t* sums, uint64_t* consts, uint64_t* pairedWsums) const {
+    OpLock g(st.get());
+    if (sums) *sums = st->fusedSums;
+    if (consts) *consts = st->fusedConsts;
+    if (pairedWsums) *pairedWsums = st->pairedWsums;
+}
+
+std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::LinearWSumRescaleMulti(
+    const std::vector<const uint64_t*>& in0, const std::vector<const uint64_t*>& in1,
+    const std::vector<std::vector<double>>& w, uint32_t level, uint32_t slots, const std::vector<double>* inScale,
+    const std::vector<double>* constants, bool* constantsAdded) {
     OpLock g(st.get());
     SfheContextState* s = st.get();
     const uint32_t ell = s->ellOf(level), n = s->n;
+    if (constantsAdded) *constantsAdded = false;
+    if (constants && constants->size() != w.size()) SFHE_THROW("LinearWSumRescaleMulti: constant count");
     const uint32_t nin = (uint32_t)in0.size(), nout = (uint32_t)w.size();
     if (ell < 2) SFHE_THROW("no levels left (multiplicative depth exhausted)");
     if (nin == 0 || nin > SFP_MAX_WSUM || nout == 0) SFHE_THROW("LinearWSumRescaleMulti: bad sizes");
@@ -3328,9 +3536,30 @@ std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::LinearWSumRescale
     // one rescale of all 2 * nout polynomials; the results share one buffer
     const size_t qw = s->polyWords(level + 1);
     auto res = s->alloc((size_t)nout * 2 * qw);
+    // the outputs' constant terms ride in the rescale's last pass where the
+    // backend has that form: per polynomial, c0 rows the constant's residues
+    // at the output scale (EvalAdd(ct, double)'s), c1 rows zero
+    std::vector<uint64_t> cst;
+    uint32_t ncst = 0;
+    if (constants && constantsAdded && psFma() && sfp_rescale_add && !s->shardAt(ell)) {
+        const uint32_t rows = s->rows(ell - 1);
+        cst.assign((size_t)2 * nout * rows, 0);
+        for (uint32_t o = 0; o < nout; ++o) {
+            if ((*constants)[o] == 0.0) continue;
+            auto k = SfheInternal::constResidues(s, (*constants)[o] * s->scale[level + 1], ell - 1);
+            std::copy(k.begin(), k.end(), cst.begin() + (size_t)2 * o * rows);
+            ++ncst;
+        }
+    }
     if (s->shardAt(ell))
         SfheInternal::rescaleShard(s, res->ptr, sums->ptr, ell, 2 * nout, pw, qw);
-    else
+    else if (ncst && sfp_rescale_add(s->dev, res->ptr, sums->ptr, ell, s->qInvTable[ell].data(), 2 * nout, pw, qw,
+                                     cst.data()) == 0) {
+        *constantsAdded = true;
+        s->fusedConsts += ncst;
+        s->stats.add += ncst;
+        s->countBytes(4.0 * (ell - 1) * n * 8 * ncst);
+    } else
         sfp_rescale(s->dev, res->ptr, sums->ptr, ell, s->qInvTable[ell].data(), 2 * nout, pw, qw);
     std::vector<Ciphertext<DCRTPoly>> out(nout);
     for (uint32_t o = 0; o < nout; ++o) {
@@ -3353,11 +3582,22 @@ std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::LinearWSumRescale
 Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::LinearWSumRescale(
     const std::vector<const uint64_t*>& in0, const std::vector<const uint64_t*>& in1,
     const std::vector<double>& w, uint32_t level, uint32_t slots, const std::vector<double>* inScale) {
+    return LinearWSumRescale(in0, in1, w, level, slots, inScale, 0.0);
+}
+
+Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::LinearWSumRescale(
+    const std::vector<const uint64_t*>& in0, const std::vector<const uint64_t*>& in1,
+    const std::vector<double>& w, uint32_t level, uint32_t slots, const std::vector<double>* inScale,
+    double constant) {
     OpLock g(st.get());
     SfheContextState* s = st.get();
     const uint32_t ell = s->ellOf(level);
     if (ell < 2) SFHE_THROW("no levels left (multiplicative depth exhausted)");
     if (inScale && inScale->size() != w.size()) SFHE_THROW("LinearWSumRescale: scale count");
+    // c0 and c1 take the same kernel over different rows: one merged launch
+    // (two virtual lanes of a batch), where no batch is open already
+    BatchScope pairLanes(this, psFma() && !s->shardAt(ell) ? 2u : 0u);
+    if (pairLanes) s->pairedWsums++;
     const size_t pw = s->polyWords(level);
     auto tmp = s->alloc(2 * pw);
     uint64_t* t0 = tmp->ptr;
@@ -3381,14 +3621,35 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::LinearWSumRescale(
             // product scale Delta_l^2 -> rescale -> Delta_{l+1}
             weightResidues(s, w[j], level, ell, kk, inScale ? (*inScale)[j] : 0.0);
         }
+        pairLanes.lane(0);
         sfp_lin_wsum(s->dev, t0, a0.data(), kk.data(), (uint32_t)a0.size(), q);
+        pairLanes.lane(1);
         sfp_lin_wsum(s->dev, t1, a1.data(), kk.data(), (uint32_t)a1.size(), q);
         s->stats.wsum_terms += take;
         s->countBytes((double)(a0.size() + 1) * 2.0 * ell * s->n * 8);
         done += take;
         first = false;
     }
-    return SfheInternal::traced(this, SfheInternal::rescale(this, t0, t1, level, slots), "LinearWSumRescale");
+    pairLanes.end();
+    // the constant term in the rescale's last pass where the backend has that
+    // form, else EvalAdd(out, constant) as before
+    std::vector<uint64_t> cst;
+    bool cstDone = false;
+    if (constant != 0.0 && psFma() && !s->shardAt(ell)) {
+        cst = SfheInternal::constResidues(s, constant * s->scale[level + 1], ell - 1);
+        cst.resize(2 * cst.size(), 0);
+    }
+    auto out = SfheInternal::traced(
+        this, SfheInternal::rescale(this, t0, t1, level, slots, cst.empty() ? nullptr : cst.data(), &cstDone),
+        "LinearWSumRescale");
+    if (cstDone) {
+        s->fusedConsts++;
+        s->stats.add++;
+        s->countBytes(4.0 * (ell - 1) * s->n * 8);
+    } else if (constant != 0.0) {
+        out = EvalAdd(out, constant);
+    }
+    return out;
 }
 
 

@@ -375,6 +375,25 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     // pairs per launch).
     std::vector<Ciphertext<DCRTPoly>> EvalMultMany(const std::vector<Ciphertext<DCRTPoly>>& a,
                                                    const std::vector<Ciphertext<DCRTPoly>>& b);
+    // Engine extension (the polynomial evaluators): EvalMult(a, b) followed by
+    // EvalAdd / EvalSub of a ciphertext r (sign < 0: subtract) and / or
+    // EvalAdd of a constant c -- the same values.  Where the product takes
+    // the fused canonical path at an unsharded level, no operand is lazy, and
+    // r is settled at exactly the product's level with that level's scale
+    // and the output's layout, the sum rides in the last pass of the
+    // product's rescale (prims.h sfp_*_add) instead of a launch of its own;
+    // everywhere else the separate ops run.  SFHE_PS_FMA=0: always separate.
+    struct MultAddend {
+        Ciphertext<DCRTPoly> r;
+        int sign = 1;
+        double c = 0.0;
+    };
+    Ciphertext<DCRTPoly> EvalMultAdd(const Ciphertext<DCRTPoly>& a, const Ciphertext<DCRTPoly>& b,
+                                     const MultAddend& add);
+    // ... for independent pairs, batched as EvalMultMany's
+    std::vector<Ciphertext<DCRTPoly>> EvalMultManyAdd(const std::vector<Ciphertext<DCRTPoly>>& a,
+                                                      const std::vector<Ciphertext<DCRTPoly>>& b,
+                                                      const std::vector<MultAddend>& adds);
     // Engine extension: sum_i a_i * p_i with ONE rescale (same value and
     // level as summing the individually rescaled EvalMult(a_i, p_i)).
     Ciphertext<DCRTPoly> EvalMultAddPlain(const std::vector<Ciphertext<DCRTPoly>>& a,
@@ -489,12 +508,29 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
                                            const std::vector<const uint64_t*>& in1,
                                            const std::vector<double>& w, uint32_t level,
                                            uint32_t slots, const std::vector<double>* inScale = nullptr);
+    // ... + constant (EvalAdd(out, constant)'s value: in the rescale's last
+    // pass where the backend has that form)
+    Ciphertext<DCRTPoly> LinearWSumRescale(const std::vector<const uint64_t*>& in0,
+                                           const std::vector<const uint64_t*>& in1,
+                                           const std::vector<double>& w, uint32_t level,
+                                           uint32_t slots, const std::vector<double>* inScale, double constant);
     // Engine extension: nout weighted sums of the same inputs in one pass
     // (one multi-output kernel + one batched rescale); w[o] has nin weights.
     std::vector<Ciphertext<DCRTPoly>> LinearWSumRescaleMulti(
         const std::vector<const uint64_t*>& in0, const std::vector<const uint64_t*>& in1,
         const std::vector<std::vector<double>>& w, uint32_t level, uint32_t slots,
         const std::vector<double>* inScale = nullptr);
+    // ... with output o's constant term constants[o]: *constantsAdded = true
+    // when the rescale's last pass added them all, false when none was added
+    // (the caller then adds them: EvalAdd(out[o], constants[o]))
+    std::vector<Ciphertext<DCRTPoly>> LinearWSumRescaleMulti(
+        const std::vector<const uint64_t*>& in0, const std::vector<const uint64_t*>& in1,
+        const std::vector<std::vector<double>>& w, uint32_t level, uint32_t slots,
+        const std::vector<double>* inScale, const std::vector<double>* constants, bool* constantsAdded);
+    // Engine internal (SFHE_PS_DEBUG): sums the backend has folded into a
+    // producing op's last pass so far -- ciphertext addends, constants -- and
+    // weighted sums whose two polynomials went out as one launch
+    void FusedSumCounts(uint64_t* sums, uint64_t* consts, uint64_t* pairedWsums) const;
     // Wait for all device work; throws on an asynchronous device error.
     void Synchronize();
     // Lazy rescaling: compute / rescale ct's rows now (canonical form at its
@@ -604,6 +640,7 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     void CopyCiphertextInto(const Ciphertext<DCRTPoly>& dst, const Ciphertext<DCRTPoly>& src);
 
   private:
+    bool multAddFusable(const Ciphertext<DCRTPoly>& a, const Ciphertext<DCRTPoly>& b, const MultAddend& add) const;
     std::unique_ptr<SfheContextState> st;
     uint32_t enabled = 0;
     BootstrapTap bootTap;
@@ -624,6 +661,10 @@ class BatchScope {
     explicit operator bool() const { return on_; }
     void lane(uint32_t i) {
         if (on_) cc_->BatchLane(i);
+    }
+    void end() {  // before the scope's end
+        if (on_) cc_->EndBatch();
+        on_ = false;
     }
 
   private:

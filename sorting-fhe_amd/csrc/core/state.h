@@ -195,7 +195,11 @@ struct SfheContextState {
     // >0: products inside the current region are formed canonically (lazy
     // rescaling held off; the Chebyshev PS evaluator, see chebyshev.cpp)
     uint32_t lazyHold = 0;
-    std::set<uint64_t> abandonedEpochs;         // captures that were abandoned (their work never ran)
+    // sums the backend folded into the producing op's last pass (prims.h
+    // sfp_*_add): ciphertext addends, constants, and weighted sums whose two
+    // polynomials went out as one launch (reported under SFHE_PS_DEBUG)
+    uint64_t fusedSums = 0, fusedConsts = 0, pairedWsums = 0;
+    std::set<uint64_t> abandonedEpochs;        // captures that were abandoned (their work never ran)
     std::vector<std::pair<uint64_t*, size_t>> capAllocs;
     std::unordered_map<uint64_t*, bool> graphOwned;
 
@@ -299,6 +303,17 @@ inline uint32_t batchWidth() {
         return (uint32_t)std::max(2L, std::min<long>(x, SFP_BATCH_MAX));
     }();
     return w;
+}
+
+// SFHE_PS_FMA=0: the polynomial evaluators' sums after a product or a rescale
+// stay separate launches instead of riding in that op's last pass, and a
+// weighted sum's two polynomials stay two launches (A/B knob; the same values)
+inline bool psFma() {
+    static const bool on = [] {
+        const char* v = std::getenv("SFHE_PS_FMA");
+        return !v || *v != '0';
+    }();
+    return on;
 }
 
 // Serialises host-side use of a context and routes the calling thread's

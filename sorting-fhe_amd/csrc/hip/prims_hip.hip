@@ -814,10 +814,23 @@ struct RowGroup {
     const double *cmD, *cmQ, *chD, *chQ;
     const u64* cmI;
     uint32_t cRows, cBig;
-    // inverse COL pass: scale row i by post_i (n^-1 times the conversion's
-    // source factor) instead of n^-1; FP64 rows are stored as doubles
-    const u64 *postK, *postKS;
-    const double *postD, *postQ;
+    // Two sets of fields that never meet share their 32 bytes (eight groups
+    // by value must stay inside the 4 KB of kernel arguments):
+    //   inverse COL pass: scale row i by post_i (n^-1 times the conversion's
+    //   source factor) instead of n^-1; FP64 rows are stored as doubles
+    //   forward epilogue (epi): after the eadd / tensor step, eout +-= esum
+    //   (a second ciphertext's rows; esumNeg: subtract) and eout += ecst[p R + i]
+    //   (per-row constants, 0 for a polynomial without one; device array)
+    union {
+        struct {
+            const u64 *postK, *postKS;
+            const double *postD, *postQ;
+        };
+        struct {
+            RowPtr esum;
+            const u64* ecst;
+        };
+    };
     // ModDown's conversion fused into the forward COL pass (k_moddown_col):
     // the per-level table (device); the call's rows ride in fields the
     // forward pass's first half otherwise uses: copy = the K source (P) rows
@@ -829,6 +842,7 @@ struct RowGroup {
     // inverse twiddles iTw / iTwS / iTwD, n^-1) in its prologue, then lifts:
     // a rescale's dropped row never makes the inverse COL round trip
     uint32_t icol;
+    uint32_t esumNeg;
     const u64 *iTw, *iTwS;
     const double* iTwD;
 };
@@ -866,6 +880,8 @@ __device__ __forceinline__ uint32_t argSel(const ArgSet<T, NG>& S, uint32_t& row
 }
 template <int NG>
 using RowGroupSet = ArgSet<RowGroup, NG>;
+// (k_ntt's other arguments take 96 bytes)
+static_assert(sizeof(RowGroupSet<8>) + 96 <= 4096, "eight row groups by value exceed the kernel-argument limit");
 
 __device__ __forceinline__ u64* rowAt(const RowPtr& r, uint32_t p, uint32_t i) {
     return const_cast<u64*>(r.base) + p * r.ps + i * r.is;
@@ -1243,6 +1259,9 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
     const u64 emk = emK ? G.emK[ii] : 0, emkS = emK ? G.emKS[ii] : 0;
     const sf_barrett EB = (emul || tens) ? loadBar(bar, prime) : sf_barrett{};
     const size_t trow = (size_t)ii << logn;
+    // (forward passes only: the inverse COL pass keeps its post factors in these fields)
+    const u64* esm = !INV && epi && G.esum.base ? rowAt(G.esum, pp, ii) : nullptr;
+    const u64 ecs = !INV && epi && G.ecst ? G.ecst[pp * G.R + ii] : 0;
 #pragma unroll
     for (int k = 0; k < NPAIR; ++k) {
         const uint32_t e = 2 * (threadIdx.x + k * NT);
@@ -1318,6 +1337,15 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
                 }
                 x.x = sf_add(x.x, sf_mul_shoup(o.x, ek2, ek2S, q), q);
                 x.y = sf_add(x.y, sf_mul_shoup(o.y, ek2, ek2S, q), q);
+            }
+            if (esm) {  // (read here, as ein is: never issued with the tile)
+                const ulonglong2 r = *reinterpret_cast<const ulonglong2*>(esm + g);
+                x.x = G.esumNeg ? sf_sub(x.x, r.x, q) : sf_add(x.x, r.x, q);
+                x.y = G.esumNeg ? sf_sub(x.y, r.y, q) : sf_add(x.y, r.y, q);
+            }
+            if (ecs) {
+                x.x = sf_add(x.x, ecs, q);
+                x.y = sf_add(x.y, ecs, q);
             }
         }
         *reinterpret_cast<ulonglong2*>(out + g) = x;
@@ -1542,7 +1570,7 @@ __global__ __launch_bounds__(TILE >> 2) void k_modup_col(const RowGroupSet<NG> G
 // rings the reference's k-way unit tests use, 2^10): the whole row in LDS, every
 // stage in one block, exact radix-2 butterflies (the oracle's schedule, so
 // canonical outputs), the same prologue (copy / pre / preK / lift) and
-// epilogue (epi / emul / emK / addMask / eadd) as the two-pass kernel.  Not a
+// epilogue (epi / emul / emK / addMask / eadd / esum / ecst) as the two-pass kernel.  Not a
 // performance path: one 256-thread block per row.
 constexpr int kNttSmallThreads = 256;
 template <bool INV>
@@ -1611,6 +1639,8 @@ __global__ __launch_bounds__(kNttSmallThreads) void k_ntt_small(const RowGroup G
     const bool emK = epi && G.emK;
     const u64 emk = emK ? G.emK[ii] : 0, emkS = emK ? G.emKS[ii] : 0;
     const sf_barrett EB = emul ? loadBar(bar, prime) : sf_barrett{};
+    const u64* esm = !INV && epi && G.esum.base ? rowAt(G.esum, pp, ii) : nullptr;
+    const u64 ecs = !INV && epi && G.ecst ? G.ecst[pp * G.R + ii] : 0;
     for (uint32_t x = threadIdx.x; x < n; x += kNttSmallThreads) {
         u64 v = s[x];
         if (INV) v = sf_mul_shoup(v, ninv[prime], ninvS[prime], q);
@@ -1621,6 +1651,8 @@ __global__ __launch_bounds__(kNttSmallThreads) void k_ntt_small(const RowGroup G
             v = sf_mul_shoup(sf_sub(a, v, q), ek, ekS, q);
             if ((G.addMask >> pp) & 1u) v = sf_add(v, out[x], q);
             if (ead) v = sf_add(v, sf_mul_shoup(ead[x], ek2, ek2S, q), q);
+            if (esm) v = G.esumNeg ? sf_sub(v, esm[x], q) : sf_add(v, esm[x], q);
+            if (ecs) v = sf_add(v, ecs, q);
         }
         out[x] = v;
     }
@@ -5591,7 +5623,7 @@ void sfp_rescale(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, co
 // multiplied on its INTT's load, the kept rows in the epilogue.
 static void rescaleCore(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, uint32_t dropPrime,
                         const uint64_t* qlinv, uint32_t npoly, size_t inStride, size_t outStride,
-                        const uint64_t* mulRows, const uint64_t* mulK) {
+                        const uint64_t* mulRows, const uint64_t* mulK, const uint64_t* cst = nullptr) {
     const uint32_t n = d->n;
     const uint32_t cnt = ell - 1;
     if (cnt > SFP_MAX_LIMBS || ell < 2) {
@@ -5655,7 +5687,14 @@ static void rescaleCore(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t 
         B.emK = dmk;
         B.emKS = dmk + cnt;
     }
+    if (cst) B.ecst = devConst(d, cst, (size_t)npoly * cnt);  // (+ per-row constants: sfp_rescale_add)
     nttRows(d, B, 0);
+}
+
+int sfp_rescale_add(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, const uint64_t* qlinv,
+                    uint32_t npoly, size_t inStride, size_t outStride, const uint64_t* cst) {
+    rescaleCore(d, out, in, ell, ell - 1, qlinv, npoly, inStride, outStride, nullptr, nullptr, cst);
+    return 0;
 }
 
 void sfp_rescale_ext(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, uint32_t dropPrime,
@@ -6411,12 +6450,28 @@ static bool mdrsiOn() {
     return on;
 }
 
+// The epilogue's addend (RowGroup::esum / ecst): rows (r0, r1) of a second
+// ciphertext added (sign >= 0) or subtracted, and `cst` -- host residues,
+// rows per polynomial for npoly polynomials -- added; either may be null.
+struct EpiAdd {
+    const uint64_t *r0 = nullptr, *r1 = nullptr;
+    int sign = 1;
+    const uint64_t* cst = nullptr;
+};
+static void epiAddInto(sfp_dev* d, RowGroup& B, const EpiAdd& e, uint32_t npoly, uint32_t rows) {
+    if (e.r0) {
+        B.esum = RowPtr{e.r0, e.r1 ? (long long)(e.r1 - e.r0) : 0, (long long)d->n};
+        B.esumNeg = e.sign < 0 ? 1u : 0u;
+    }
+    if (e.cst) B.ecst = devConst(d, e.cst, (size_t)npoly * rows);
+}
+
 // sfp_moddown_rescale; T[4] (a0, a1, b0, b1) non-null: d0 / d1 are the
 // tensor of (a0, a1) and (b0, b1), formed in the final pass's epilogue
 static void moddownRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* d0, const uint64_t* d1,
                                const uint64_t* const* T, uint64_t* acc, size_t accStride, uint32_t ell, uint32_t K,
                                uint32_t Lq, const sfp_conv* c, const uint64_t* pinv, const uint64_t* pmod,
-                               const uint64_t* qlinv, uint64_t* scr, int rowDone) {
+                               const uint64_t* qlinv, uint64_t* scr, int rowDone, const EpiAdd& ea = EpiAdd{}) {
     const uint32_t n = d->n, l = ell - 1;
     if (ell < 2 || ell > SFP_MAX_LIMBS || !c || c->ns > (uint32_t)kMaxConvSrc || c->nt < ell ||
         !limbsOk(d, sfp_limbs{K + 1, 1, Lq, l}, "moddown_rescale")) {
@@ -6545,6 +6600,7 @@ static void moddownRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, const
     B.kS = devConst(d, k1S, l);
     B.k2 = devConst(d, qlinv, l);
     B.k2S = devConst(d, k2S, l);
+    epiAddInto(d, B, ea, 2, l);
     nttRows(d, B, 0);
 }
 
@@ -6556,11 +6612,11 @@ void sfp_moddown_rescale(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint6
                        rowDone);
 }
 
-int sfp_mult_relin_rescale(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* a0, const uint64_t* a1,
-                           const uint64_t* b0, const uint64_t* b1, uint32_t ell, uint32_t K, uint32_t Lq,
-                           uint32_t alpha, const sfp_conv* const* convs, const uint64_t* key, const sfp_conv* c,
-                           const uint64_t* pinv, const uint64_t* pmod, const uint64_t* qlinv, uint64_t* acc,
-                           uint64_t* ext, uint64_t* scr) {
+static int multRelinRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* a0, const uint64_t* a1,
+                                const uint64_t* b0, const uint64_t* b1, uint32_t ell, uint32_t K, uint32_t Lq,
+                                uint32_t alpha, const sfp_conv* const* convs, const uint64_t* key, const sfp_conv* c,
+                                const uint64_t* pinv, const uint64_t* pmod, const uint64_t* qlinv, uint64_t* acc,
+                                uint64_t* ext, uint64_t* scr, const EpiAdd& ea) {
     const uint32_t beta = (ell + alpha - 1) / alpha;
     if (!ksFuse() || d->n <= (uint32_t)kNttTile) return -1;
     if (ell < 2 || beta > (uint32_t)kMaxConvJobs || ell + K > SFP_MAX_LIMBS) {
@@ -6573,7 +6629,50 @@ int sfp_mult_relin_rescale(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uin
     modupInnerCore(d, acc, acc + (size_t)(ell + K) * d->n, a1, b1, ell, K, Lq, alpha, convs, key, nullptr, nullptr,
                    T, pmod[ell - 1], 0, ell - 1, ext, scr);
     moddownRescaleCore(d, out0, out1, nullptr, nullptr, T, acc, (size_t)(ell + K) * d->n, ell, K, Lq, c, pinv, pmod,
-                       qlinv, scr, 1);
+                       qlinv, scr, 1, ea);
+    return 0;
+}
+
+int sfp_mult_relin_rescale(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* a0, const uint64_t* a1,
+                           const uint64_t* b0, const uint64_t* b1, uint32_t ell, uint32_t K, uint32_t Lq,
+                           uint32_t alpha, const sfp_conv* const* convs, const uint64_t* key, const sfp_conv* c,
+                           const uint64_t* pinv, const uint64_t* pmod, const uint64_t* qlinv, uint64_t* acc,
+                           uint64_t* ext, uint64_t* scr) {
+    return multRelinRescaleCore(d, out0, out1, a0, a1, b0, b1, ell, K, Lq, alpha, convs, key, c, pinv, pmod, qlinv,
+                                acc, ext, scr, EpiAdd{});
+}
+
+// The epilogue addend's constants cover both polynomials: c1 carries zeros.
+static const uint64_t* cstBoth(const uint64_t* cst, uint32_t rows, uint64_t* buf) {
+    if (!cst) return nullptr;
+    for (uint32_t i = 0; i < rows; ++i) {
+        buf[i] = cst[i];
+        buf[rows + i] = 0;
+    }
+    return buf;
+}
+
+int sfp_mult_relin_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* a0, const uint64_t* a1,
+                               const uint64_t* b0, const uint64_t* b1, uint32_t ell, uint32_t K, uint32_t Lq,
+                               uint32_t alpha, const sfp_conv* const* convs, const uint64_t* key, const sfp_conv* c,
+                               const uint64_t* pinv, const uint64_t* pmod, const uint64_t* qlinv, uint64_t* acc,
+                               uint64_t* ext, uint64_t* scr, const uint64_t* r0, const uint64_t* r1, int sign,
+                               const uint64_t* cst) {
+    uint64_t kb[2 * SFP_MAX_LIMBS];
+    if (ell < 2 || ell > SFP_MAX_LIMBS) return -1;
+    return multRelinRescaleCore(d, out0, out1, a0, a1, b0, b1, ell, K, Lq, alpha, convs, key, c, pinv, pmod, qlinv,
+                                acc, ext, scr, EpiAdd{r0, r1, sign, cstBoth(cst, ell - 1, kb)});
+}
+
+int sfp_moddown_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* d0, const uint64_t* d1,
+                            uint64_t* acc, size_t accStride, uint32_t ell, uint32_t K, uint32_t Lq,
+                            const sfp_conv* c, const uint64_t* pinv, const uint64_t* pmod, const uint64_t* qlinv,
+                            uint64_t* scr, int rowDone, const uint64_t* r0, const uint64_t* r1, int sign,
+                            const uint64_t* cst) {
+    uint64_t kb[2 * SFP_MAX_LIMBS];
+    if (ell < 2 || ell > SFP_MAX_LIMBS) return -1;
+    moddownRescaleCore(d, out0, out1, d0, d1, nullptr, acc, accStride, ell, K, Lq, c, pinv, pmod, qlinv, scr,
+                       rowDone, EpiAdd{r0, r1, sign, cstBoth(cst, ell - 1, kb)});
     return 0;
 }
 

@@ -302,6 +302,37 @@ int sfp_mult_relin_rescale(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uin
                            const uint64_t* pinv, const uint64_t* pmod, const uint64_t* qlinv, uint64_t* acc,
                            uint64_t* ext, uint64_t* scratch);
 
+// ---- optional: a sum folded into the producing op's last pass ---------------
+// Weak declarations: a backend may leave them out (the C oracle does).  The
+// host layer calls one only where its address is non-null and, where it
+// returns -1 (no fused form here, nothing done), runs the producing prim
+// followed by sfp_add / sfp_sub / sfp_add_const -- the same integers, as the
+// sum is one modular addition on the canonical residue the last pass stores.
+//   (r0, r1): rows of a ciphertext at the output's limb count, added (sign
+//   >= 0) or subtracted (sign < 0); may be null.
+//   cst: host residues added per row (null: none) -- ell - 1 of them for
+//   polynomial 0 in the two relinearising forms, npoly * (ell - 1) (polynomial
+//   major; 0 where a polynomial has none) in sfp_rescale_add.
+#if defined(__GNUC__)
+#define SFP_OPTIONAL __attribute__((weak))
+#else
+#define SFP_OPTIONAL
+#endif
+SFP_OPTIONAL int sfp_mult_relin_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* a0,
+                                            const uint64_t* a1, const uint64_t* b0, const uint64_t* b1, uint32_t ell,
+                                            uint32_t K, uint32_t Lq, uint32_t alpha, const sfp_conv* const* convs,
+                                            const uint64_t* key, const sfp_conv* c, const uint64_t* pinv,
+                                            const uint64_t* pmod, const uint64_t* qlinv, uint64_t* acc, uint64_t* ext,
+                                            uint64_t* scratch, const uint64_t* r0, const uint64_t* r1, int sign,
+                                            const uint64_t* cst);
+SFP_OPTIONAL int sfp_moddown_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* d0,
+                                         const uint64_t* d1, uint64_t* acc, size_t acc_stride, uint32_t ell,
+                                         uint32_t K, uint32_t Lq, const sfp_conv* c, const uint64_t* pinv,
+                                         const uint64_t* pmod, const uint64_t* qlinv, uint64_t* scratch, int row_done,
+                                         const uint64_t* r0, const uint64_t* r1, int sign, const uint64_t* cst);
+SFP_OPTIONAL int sfp_rescale_add(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, const uint64_t* qlinv,
+                                 uint32_t npoly, size_t in_stride, size_t out_stride, const uint64_t* cst);
+
 // ---- sampling (counter-based, deterministic) ------------------------------------
 // Uniform residues mod each limb's prime: value for (limb, i) is derived from
 // splitmix64(seed, stream-id = prime index, i); identical on every backend.
