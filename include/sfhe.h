@@ -26,6 +26,8 @@ extern "C" {
 #endif
 
 #define SFHE_ABI_VERSION 3  /* bumped when a declaration or struct below changes */
+/* (sfhe_decrypt_batch and sfhe_decode_counts were added at version 3: additions
+ * only, no existing declaration changed, so the version stays) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -97,6 +99,10 @@ int sfhe_bootstrap_graphs(sfhe_ctx* c, uint64_t* count);
 /* Plaintext encodings done on the device (sfp_encode) and on the host since
  * the last sfhe_op_stats reset. */
 int sfhe_encode_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host);
+/* Ciphertexts whose decryption was decoded on the device (sfp_decode_batch)
+ * and on the host since the last sfhe_op_stats reset (SFHE_DEV_DECODE=0, read
+ * per call, decodes on the host; the results are bit-identical). */
+int sfhe_decode_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host);
 /* Device memory held by the context's buffer pool (live and free blocks). */
 int sfhe_pool_bytes(sfhe_ctx* c, uint64_t* bytes);
 /* Engine contexts alive in this process (diagnostics: after every
@@ -139,6 +145,12 @@ int sfhe_encrypt(sfhe_ctx* c, const double* values, size_t len, uint32_t slots, 
                  sfhe_ct** out);
 /* writes min(cap, slots) real parts; *len = slots */
 int sfhe_decrypt(sfhe_ctx* c, const sfhe_ct* ct, double* out, size_t cap, size_t* len);
+/* `count` ciphertexts (any mix of levels and slot counts) decrypted with one
+ * device synchronisation: the real parts of ciphertext k go to out + k * stride
+ * (at most `stride` values each), lens[k] = its slot count (lens may be NULL).
+ * The values equal sfhe_decrypt's on each ciphertext. */
+int sfhe_decrypt_batch(sfhe_ctx* c, const sfhe_ct* const* cts, size_t count, double* out, size_t stride,
+                       size_t* lens);
 void sfhe_ct_free(sfhe_ct* ct);
 int sfhe_ct_clone(const sfhe_ct* ct, sfhe_ct** out);
 /* Ciphertext::GetLevel / GetSlots / limb count */

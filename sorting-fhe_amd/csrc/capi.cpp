@@ -304,6 +304,33 @@ int sfhe_decrypt(sfhe_ctx* c, const sfhe_ct* ct, double* out, size_t cap, size_t
     });
 }
 
+int sfhe_decrypt_batch(sfhe_ctx* c, const sfhe_ct* const* cts, size_t count, double* out, size_t stride,
+                       size_t* lens) {
+    REQUIRE(c && (cts || !count), "null argument");
+    REQUIRE(out || !stride || !count, "null output with a non-zero stride");
+    REQUIRE(c->keys.secretKey, "no secret key");
+    for (size_t k = 0; k < count; ++k) REQUIRE(cts[k], "null ciphertext");
+    return guard([&] {
+        std::vector<Ciphertext<DCRTPoly>> in(count);
+        for (size_t k = 0; k < count; ++k) in[k] = cts[k]->ct;
+        std::vector<Plaintext> pts;
+        c->cc->DecryptMany(c->keys.secretKey, in, &pts);
+        for (size_t k = 0; k < count; ++k) {
+            const auto& v = pts[k]->GetRealPackedValue();
+            if (lens) lens[k] = v.size();
+            for (size_t i = 0; i < v.size() && i < stride; ++i) out[k * stride + i] = v[i];
+        }
+    });
+}
+
+int sfhe_decode_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host) {
+    REQUIRE(c && device && host, "null argument");
+    auto s = c->cc->GetOpStats();
+    *device = s.dev_decodes;
+    *host = s.host_decodes;
+    return SFHE_OK;
+}
+
 void sfhe_ct_free(sfhe_ct* ct) { delete ct; }
 
 int sfhe_ct_clone(const sfhe_ct* ct, sfhe_ct** out) {

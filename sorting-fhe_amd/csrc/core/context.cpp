@@ -2454,21 +2454,24 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::Encrypt(const PublicKey<DCRTPo
     return SfheInternal::traced(this, ct, "Encrypt");
 }
 
-void CryptoContextImpl<DCRTPoly>::Decrypt(const PrivateKey<DCRTPoly>& sk,
-                                          const Ciphertext<DCRTPoly>& ct, Plaintext* out) {
-    OpLock g(st.get());
-    SfheInternal::deps(st.get(), {&ct});
-    SfheContextState* s = st.get();
-    if (!sk) SFHE_THROW("null secret key");
-    if (s->sharded) {  // every rank gathers the rows and decrypts
-        auto full = SfheInternal::gatherFull(s, ct);
-        FullScope fs(s);
-        auto fc = std::make_shared<CiphertextImpl<DCRTPoly>>(*ct);
-        fc->buf = full;
-        fc->c0 = full->ptr;
-        fc->c1 = fc->c0 + (size_t)s->ellOf(ct->level) * s->n;
-        return Decrypt(sk, fc, out);
-    }
+namespace {
+
+// The decryption's plaintext from its decoded slots, with the precision
+// estimate from the imaginary parts (inputs are real)
+Plaintext decodedPlaintext(const std::vector<std::complex<double>>& vals, uint32_t slots, uint32_t level) {
+    auto pt = std::make_shared<PlaintextImpl>(vals, slots, level);
+    double var = 0;
+    for (auto& z : vals) var += z.imag() * z.imag();
+    double sd = std::sqrt(var / std::max<size_t>(1, vals.size()));
+    pt->logError = sd > 0 ? std::log2(sd) : -60.0;
+    pt->logPrecision = -pt->logError;
+    return pt;
+}
+
+// Decrypt with the decoding on the host (the oracle's path, and the product's
+// with SFHE_DEV_DECODE=0): c0 + c1 s and its inverse NTT on the device, the
+// CRT lift, the centring and the special FFT here.
+Plaintext decryptHostDecode(SfheContextState* s, const PrivateKey<DCRTPoly>& sk, const Ciphertext<DCRTPoly>& ct) {
     const uint32_t ell = s->ellOf(ct->level);
     const uint32_t nl = std::min<uint32_t>(2, ell);
     const sfp_limbs q = SfheInternal::Q(nl);
@@ -2514,14 +2517,115 @@ void CryptoContextImpl<DCRTPoly>::Decrypt(const PrivateKey<DCRTPoly>& sk,
     }
     std::vector<std::complex<double>> vals;
     ckks_decode(c, ct->slots, s->n, vals);
-    auto pt = std::make_shared<PlaintextImpl>(vals, ct->slots, ct->level);
-    // precision estimate from the imaginary parts (inputs are real)
-    double var = 0;
-    for (auto& z : vals) var += z.imag() * z.imag();
-    double sd = std::sqrt(var / std::max<size_t>(1, vals.size()));
-    pt->logError = sd > 0 ? std::log2(sd) : -60.0;
-    pt->logPrecision = -pt->logError;
-    *out = pt;
+    s->stats.host_decodes++;
+    return decodedPlaintext(vals, ct->slots, ct->level);
+}
+
+// The device decoder is used where the backend has one (prims.h
+// sfp_decode_batch) unless SFHE_DEV_DECODE=0 (read per call: one process can
+// compare the two paths).
+bool deviceDecode(const Ciphertext<DCRTPoly>& ct) {
+    if (!sfp_decode_batch) return false;
+    const char* v = std::getenv("SFHE_DEV_DECODE");
+    if (v && *v == '0') return false;
+    return ct->slots && !(ct->slots & (ct->slots - 1));
+}
+
+// outs[k] = the decryption of cts[k] (unsharded rows, at most kDecryptChunk of
+// them).  Device decoding: the ciphertexts are grouped by (slots, limbs); each
+// group's c0 + c1 s go to consecutive 2n-word row sets, with one batched
+// inverse NTT and one decode per group, then ONE download of every group's
+// slots (the only synchronisation).
+constexpr size_t kDecryptChunk = 128;
+void decryptRows(SfheContextState* s, const PrivateKey<DCRTPoly>& sk, const Ciphertext<DCRTPoly>* cts, size_t count,
+                 Plaintext* outs) {
+    std::map<std::pair<uint32_t, uint32_t>, std::vector<size_t>> groups;  // (slots, nl) -> indices
+    size_t ndev = 0, words = 0;
+    for (size_t k = 0; k < count; ++k) {
+        if (!deviceDecode(cts[k])) continue;
+        groups[{cts[k]->slots, std::min<uint32_t>(2, s->ellOf(cts[k]->level))}].push_back(k);
+        ++ndev;
+        words += (size_t)2 * cts[k]->slots;
+    }
+    if (ndev) {
+        const size_t stride = (size_t)2 * s->n;
+        auto t = s->alloc(ndev * stride);
+        auto dec = s->alloc(words);
+        size_t row = 0, off = 0;
+        for (auto& g : groups) {
+            const uint32_t slots = g.first.first, nl = g.first.second;
+            const sfp_limbs q = SfheInternal::Q(nl);
+            uint64_t* base = t->ptr + row * stride;
+            std::vector<double> scales;
+            for (size_t k : g.second) {
+                sfp_mul_add(s->dev, t->ptr + row * stride, cts[k]->c1, sk->s->ptr, cts[k]->c0, q);
+                scales.push_back(cts[k]->scale);
+                ++row;
+            }
+            const uint32_t cnt = (uint32_t)g.second.size();
+            sfp_ntt_batch(s->dev, base, stride, cnt, q, 1);
+            sfp_decode_batch(s->dev, base, stride, cnt, nl, slots, scales.data(),
+                             reinterpret_cast<double*>(dec->ptr + off));
+            off += (size_t)cnt * 2 * slots;
+        }
+        std::vector<std::complex<double>> all(words / 2);
+        sfp_d2h(s->dev, all.data(), dec->ptr, words * 8);
+        const char* err = sfp_last_error(s->dev);
+        if (err) SFHE_THROW(std::string("device error: ") + err);
+        size_t at = 0;
+        for (auto& g : groups)
+            for (size_t k : g.second) {
+                const uint32_t slots = g.first.first;
+                std::vector<std::complex<double>> vals(all.begin() + at, all.begin() + at + slots);
+                at += slots;
+                outs[k] = decodedPlaintext(vals, slots, cts[k]->level);
+                s->stats.dev_decodes++;
+            }
+    }
+    for (size_t k = 0; k < count; ++k)
+        if (!outs[k]) outs[k] = decryptHostDecode(s, sk, cts[k]);
+}
+
+}  // namespace
+
+void CryptoContextImpl<DCRTPoly>::DecryptMany(const PrivateKey<DCRTPoly>& sk,
+                                              const std::vector<Ciphertext<DCRTPoly>>& cts,
+                                              std::vector<Plaintext>* outs) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    if (!sk) SFHE_THROW("null secret key");
+    if (!outs) SFHE_THROW("null output");
+    for (const auto& ct : cts)
+        if (!ct) SFHE_THROW("null ciphertext");
+    SfheInternal::depsv(s, cts);
+    outs->assign(cts.size(), nullptr);
+    for (size_t k0 = 0; k0 < cts.size(); k0 += kDecryptChunk) {
+        const size_t cnt = std::min(kDecryptChunk, cts.size() - k0);
+        if (!s->sharded) {
+            decryptRows(s, sk, cts.data() + k0, cnt, outs->data() + k0);
+            continue;
+        }
+        // every rank gathers the rows and decrypts
+        std::vector<Ciphertext<DCRTPoly>> full(cnt);
+        for (size_t k = 0; k < cnt; ++k) {
+            const auto& ct = cts[k0 + k];
+            auto rows = SfheInternal::gatherFull(s, ct);
+            auto fc = std::make_shared<CiphertextImpl<DCRTPoly>>(*ct);
+            fc->buf = rows;
+            fc->c0 = rows->ptr;
+            fc->c1 = fc->c0 + (size_t)s->ellOf(ct->level) * s->n;
+            full[k] = fc;
+        }
+        FullScope fs(s);
+        decryptRows(s, sk, full.data(), cnt, outs->data() + k0);
+    }
+}
+
+void CryptoContextImpl<DCRTPoly>::Decrypt(const PrivateKey<DCRTPoly>& sk,
+                                          const Ciphertext<DCRTPoly>& ct, Plaintext* out) {
+    std::vector<Plaintext> outs;
+    DecryptMany(sk, {ct}, &outs);
+    *out = outs[0];
 }
 
 const std::vector<double>& PlaintextImpl::GetRealPackedValue() const {

@@ -330,6 +330,13 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     void Decrypt(const Ciphertext<DCRTPoly>& ct, const PrivateKey<DCRTPoly>& sk, Plaintext* out) {
         Decrypt(sk, ct, out);
     }
+    // Engine extension: outs[k] = the decryption of cts[k] (any mix of levels
+    // and slot counts), the same plaintexts as Decrypt on each.  Where the
+    // backend decodes on the device (prims.h sfp_decode_batch) the batch costs
+    // one inverse NTT and one decode per (slots, limbs) group, one download and
+    // one synchronisation; elsewhere it is a loop over Decrypt.
+    void DecryptMany(const PrivateKey<DCRTPoly>& sk, const std::vector<Ciphertext<DCRTPoly>>& cts,
+                     std::vector<Plaintext>* outs);
 
     // additive
     Ciphertext<DCRTPoly> EvalAdd(const Ciphertext<DCRTPoly>& a, const Ciphertext<DCRTPoly>& b);
@@ -605,6 +612,7 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         uint64_t keyswitch = 0, rescale = 0, tensor = 0, ptmult = 0, constmult = 0, add = 0,
                  automorph = 0, ntt_limbs = 0, wsum_terms = 0;
         uint64_t dev_encodes = 0, host_encodes = 0;  // plaintext encodings on the device / host
+        uint64_t dev_decodes = 0, host_decodes = 0;  // decrypted ciphertexts decoded on the device / host
         double algo_bytes = 0.0;  // SURVEY.md §8(d) byte model
         uint64_t pool_bytes = 0;  // device memory held by the context's pool (live + free blocks)
     };
@@ -689,7 +697,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 5
+#define SFHE_FACADE_ABI_VERSION 6
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

@@ -6856,6 +6856,153 @@ void sfp_encode(sfp_dev* d, uint64_t* dst, const double* vals, uint32_t nvals, i
     sfp_encode_batch(d, dst, 0, vals, nvals, 1, real, slots, scale, m, scratch);
 }
 
+// ---- CKKS decoding on the device (the end of a decryption) ------------------
+// The host path of CryptoContextImpl::Decrypt, operation for operation: the
+// CRT lift and centring of the needed coefficients, their conversion to double
+// (one rounding), the division by the scale, then the special FFT of
+// core/encoder.cpp fftSpecial -- its bit reversal folded into the load, its
+// stages in its order with its integer twiddle index, w = b * ksi formed as
+// (re re - im im, re im + im re) with no fused multiply-add, then u + w and
+// u - w.  Stages that fit kEncTile values run in LDS, one tile per block; the
+// stages above them run one kernel per stage (k_enc_tile / k_enc_stage in
+// reverse order).
+__device__ __forceinline__ void decButterfly(double2& a, double2& b, uint32_t j, uint32_t len, const u64* rot,
+                                             const double2* ksi, u64 M) {
+#pragma clang fp contract(off)
+    const u64 lenq = (u64)len << 2;
+    const u64 idx = (rot[j] & (lenq - 1)) * (M / lenq);
+    const double2 k = ksi[idx];
+    const double2 u = a;
+    const double wre = b.x * k.x - b.y * k.y;
+    const double wim = b.x * k.y + b.y * k.x;
+    a = make_double2(u.x + wre, u.y + wim);
+    b = make_double2(u.x - wre, u.y - wim);
+}
+
+// x < 2^127 as a double with ONE round-to-nearest-even, as the host's
+// u128 -> double conversion: the top 64 bits of the normalised value with the
+// discarded bits ORed into bit 0 (eleven places below the rounding position,
+// so it only ever breaks a tie), converted and scaled back exactly.
+__device__ __forceinline__ double decU128ToDouble(u64 lo, u64 hi) {
+    if (!hi) return (double)lo;
+    const int lz = __clzll((long long)hi);  // hi != 0: 0 <= lz < 64
+    const u64 top = lz ? (hi << lz) | (lo >> (64 - lz)) : hi;
+    const u64 rest = lo << lz;
+    return ldexp((double)(top | (rest ? 1ull : 0ull)), 64 - lz);
+}
+
+// the centred value of coefficient x of a row set (nl = 1: modulo q0; 2: the
+// CRT lift modulo Q = q0 q1), as a double
+__device__ __forceinline__ double decCentred(const u64* __restrict__ p, uint32_t x, uint32_t n, uint32_t nl,
+                                             const sf_barrett& B0, const sf_barrett& B1, u64 q0inv) {
+    const u64 a0 = p[x];
+    if (nl == 1) return a0 > B0.q / 2 ? -(double)(B0.q - a0) : (double)a0;
+    const u64 a1 = p[(size_t)n + x];
+    const u64 r0 = a0 % B1.q;
+    const u64 dd = a1 >= r0 ? a1 - r0 : a1 + B1.q - r0;
+    const u64 m = sf_mul(dd, q0inv, &B1);  // d * q0^-1 mod q1 (exact: any modular product gives the same integer)
+    // x = a0 + q0 * m < Q, against Q / 2, in two words
+    u64 lo = B0.q * m, hi = __umul64hi(B0.q, m);
+    lo += a0;
+    hi += lo < a0 ? 1 : 0;
+    const u64 Qlo = B0.q * B1.q, Qhi = __umul64hi(B0.q, B1.q);
+    const u64 Hlo = (Qlo >> 1) | (Qhi << 63), Hhi = Qhi >> 1;
+    if (hi > Hhi || (hi == Hhi && lo > Hlo)) {
+        const u64 nlo = Qlo - lo, nhi = Qhi - hi - (Qlo < lo ? 1 : 0);
+        return -decU128ToDouble(nlo, nhi);
+    }
+    return decU128ToDouble(lo, hi);
+}
+
+// v[brev(i)] = (c[i gap], c[n/2 + i gap]) / scale for the S slots of batch
+// blockIdx.y: only those 2 S words of its rows are read
+__global__ __launch_bounds__(kThreads) void k_dec_load(double2* __restrict__ v, const u64* __restrict__ src,
+                                                       size_t srcStride, uint32_t nl, uint32_t logS,
+                                                       const double* __restrict__ scales,
+                                                       const sf_barrett* __restrict__ bar, u64 q0inv,
+                                                       uint32_t logn) {
+#pragma clang fp contract(off)
+    const uint32_t n = 1u << logn, half = n >> 1, S = 1u << logS, gap = half >> logS;
+    const u64* p = src + (size_t)blockIdx.y * srcStride;
+    v += (size_t)blockIdx.y << logS;
+    const double scale = scales[blockIdx.y];
+    const sf_barrett B0 = loadBar(bar, 0), B1 = loadBar(bar, nl > 1 ? 1 : 0);
+    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < S; i += gridDim.x * kThreads) {
+        const double re = decCentred(p, i * gap, n, nl, B0, B1, q0inv);
+        const double im = decCentred(p, half + i * gap, n, nl, B0, B1, q0inv);
+        const uint32_t r = logS ? (__brev(i) >> (32 - logS)) : 0u;
+        v[r] = make_double2(re / scale, im / scale);
+    }
+}
+
+// the stages of span 2, 4, ..., T on one T-value tile per block, in LDS
+__global__ __launch_bounds__(kThreads) void k_dec_tile(double2* __restrict__ v, uint32_t T,
+                                                       const u64* __restrict__ rot, const double2* __restrict__ ksi,
+                                                       u64 M) {
+    __shared__ double2 sh[kEncTile];
+    double2* g = v + (size_t)blockIdx.y * gridDim.x * T + (size_t)blockIdx.x * T;
+    for (uint32_t i = threadIdx.x; i < T; i += kThreads) sh[i] = g[i];
+    __syncthreads();
+    for (uint32_t len = 2; len <= T; len <<= 1) {
+        const uint32_t lenh = len >> 1;
+        for (uint32_t t = threadIdx.x; t < T / 2; t += kThreads) {
+            const uint32_t j = t % lenh, i = (t / lenh) * len;
+            double2 a = sh[i + j], b = sh[i + j + lenh];
+            decButterfly(a, b, j, len, rot, ksi, M);
+            sh[i + j] = a;
+            sh[i + j + lenh] = b;
+        }
+        __syncthreads();
+    }
+    for (uint32_t i = threadIdx.x; i < T; i += kThreads) g[i] = sh[i];
+}
+
+// one stage of butterfly span `len` over the whole vector
+__global__ __launch_bounds__(kThreads) void k_dec_stage(double2* __restrict__ v, uint32_t S, uint32_t len,
+                                                        const u64* __restrict__ rot,
+                                                        const double2* __restrict__ ksi, u64 M) {
+    v += (size_t)blockIdx.y * S;
+    const uint32_t lenh = len >> 1;
+    for (uint32_t t = blockIdx.x * kThreads + threadIdx.x; t < S / 2; t += gridDim.x * kThreads) {
+        const uint32_t j = t % lenh, i = (t / lenh) * len;
+        double2 a = v[i + j], b = v[i + j + lenh];
+        decButterfly(a, b, j, len, rot, ksi, M);
+        v[i + j] = a;
+        v[i + j + lenh] = b;
+    }
+}
+
+int sfp_decode_batch(sfp_dev* d, const uint64_t* src, size_t srcStride, uint32_t count, uint32_t nl, uint32_t slots,
+                     const double* scales, double* out) {
+    if (!count) return 0;
+    if (!d->encRot || !slots || (slots & (slots - 1)) || slots > d->n / 2 || count > 65535u || nl < 1 || nl > 2 ||
+        nl > d->np) {
+        record(d, "decode (tables not set up, or a bad slot / batch / row count)", hipErrorInvalidValue);
+        return 0;
+    }
+    // q0^-1 mod q1 (Fermat: the moduli are distinct primes)
+    u64 q0inv = 0;
+    if (nl == 2) {
+        const sf_barrett& B1 = d->hbar[1];
+        q0inv = sf_pow(d->hbar[0].q % B1.q, B1.q - 2, &B1);
+    }
+    const u64 M = 2ull * d->n;
+    double2* v = reinterpret_cast<double2*>(out);
+    const double* ds = (const double*)ringPut(d, scales, (size_t)count * 8);
+    if (!ds) return 0;
+    const uint32_t logS = (uint32_t)__builtin_ctz(slots);
+    SFP_GO(k_dec_load, dim3(gridFor(slots, kThreads), count), dim3(kThreads), v, src, srcStride, nl, logS, ds,
+                       d->bar, q0inv, d->logn);
+    const uint32_t T = std::min(slots, kEncTile);
+    if (T >= 2)
+        SFP_GO(k_dec_tile, dim3(slots / T, count), dim3(kThreads), v, T, d->encRot, d->encKsi, M);
+    for (uint32_t len = 2 * T; len <= slots && len; len <<= 1)
+        SFP_GO(k_dec_stage, dim3(gridFor(slots / 2, kThreads), count), dim3(kThreads), v, slots, len,
+                           d->encRot, d->encKsi, M);
+    checkLaunch(d, "decode");
+    return 0;
+}
+
 // ---- limb sharding ----
 // dst row i = src row rows[i]
 __global__ __launch_bounds__(kThreads) void k_gather_rows(ulonglong2* __restrict__ dst,

@@ -333,6 +333,21 @@ SFP_OPTIONAL int sfp_moddown_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* o
 SFP_OPTIONAL int sfp_rescale_add(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, const uint64_t* qlinv,
                                  uint32_t npoly, size_t in_stride, size_t out_stride, const uint64_t* cst);
 
+// ---- optional: CKKS decoding on the device (the end of a decryption) ----------
+// `count` row sets src + b * srcStride, each nl (1 or 2) COEFFICIENT-domain
+// rows of n words modulo primes 0 .. nl-1 (c0 + c1 s after its inverse NTT),
+// decoded as `slots`-slot sparse packings: the centred CRT lift of the
+// coefficients i gap and n/2 + i gap (gap = n / (2 slots); nothing else is
+// read), as doubles divided by scales[b] (host array), through the special
+// FFT -- bit-identical to the host path (CryptoContextImpl::Decrypt's lift
+// followed by core/encoder.cpp ckks_decode).  out (device): count * slots
+// (re, im) pairs, batch-major; it is also the working buffer.  Needs
+// sfp_encode_setup's tables.  No host synchronisation of its own (the scales
+// travel through the argument ring).  Weak like the prims above: the host
+// layer decodes on the host where its address is null (the C oracle).
+SFP_OPTIONAL int sfp_decode_batch(sfp_dev* d, const uint64_t* src, size_t srcStride, uint32_t count, uint32_t nl,
+                                  uint32_t slots, const double* scales, double* out);
+
 // ---- sampling (counter-based, deterministic) ------------------------------------
 // Uniform residues mod each limb's prime: value for (limb, i) is derived from
 // splitmix64(seed, stream-id = prime index, i); identical on every backend.

@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "sfhe_key_rows",
     "sfhe_groups_rccl", "sfhe_groups_host", "sfhe_groups",
     "sfhe_encode_counts", "sfhe_bootstrap_graphs",
+    "sfhe_decrypt_batch", "sfhe_decode_counts",
 ]
 
 
@@ -165,6 +166,8 @@ _SIGS = {
     "sfhe_groups": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sfhe_encode_counts": (C.c_int, [_VP, _PU64, _PU64]),
     "sfhe_bootstrap_graphs": (C.c_int, [_VP, _PU64]),
+    "sfhe_decrypt_batch": (C.c_int, [_VP, C.POINTER(_VP), _SZ, _PD, _SZ, _PSZ]),
+    "sfhe_decode_counts": (C.c_int, [_VP, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -424,11 +427,29 @@ class Engine:
         return self._new(self.lib.sfhe_encrypt, self.ctx, a, len(values), slots, level)
 
     def decrypt(self, ct: "Ct") -> list:
-        n = C.c_size_t()
-        self._chk(self.lib.sfhe_decrypt(self.ctx, ct.h, None, 0, C.byref(n)))
-        buf = (C.c_double * n.value)()
-        self._chk(self.lib.sfhe_decrypt(self.ctx, ct.h, buf, n.value, None))
+        n = ct.slots  # (sfhe_decrypt writes min(cap, slots) values: decrypt once)
+        buf = (C.c_double * n)()
+        self._chk(self.lib.sfhe_decrypt(self.ctx, ct.h, buf, n, None))
         return list(buf)
+
+    def decrypt_batch(self, cts: Sequence["Ct"]) -> list:
+        """[decrypt(c) for c in cts] with one device synchronisation for the
+        whole list (any mix of levels and slot counts)."""
+        cts = list(cts)
+        if not cts:
+            return []
+        stride = max(c.slots for c in cts)
+        hs = (_VP * len(cts))(*[c.h for c in cts])
+        buf = (C.c_double * (stride * len(cts)))()
+        lens = (C.c_size_t * len(cts))()
+        self._chk(self.lib.sfhe_decrypt_batch(self.ctx, hs, len(cts), buf, stride, lens))
+        return [list(buf[k * stride:k * stride + lens[k]]) for k in range(len(cts))]
+
+    def decode_counts(self):
+        """(device, host) decodings of decrypted ciphertexts since the last op_stats reset."""
+        d, h = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_decode_counts(self.ctx, C.byref(d), C.byref(h)))
+        return d.value, h.value
 
     # -- eval --
     def add(self, a, b):
