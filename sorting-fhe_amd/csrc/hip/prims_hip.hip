@@ -429,11 +429,13 @@ static unsigned gridFor(size_t work, unsigned perBlock) {
 #endif
 constexpr int kNttTile = SFHE_NTT_TILE;         // words per tile (one block)
 constexpr int kNttRows = kNttTile / 256;        // ROW pass: whole rows per tile
-// LE = stages per register round (2^LE words per thread, kNttTile >> LE
-// threads).  Launches below kNttSmallRows rows run LE = 2 (twice the waves per
-// tile), larger ones LE = 3 (fewer rounds and barriers).  Measured on the
-// sort (N=256 @ 2^16): thresholds 6 / 12 / 24 / 36 / all rows gave 64.6 / 63.8 /
-// 63.3 / 62.5 / 62.2 ms, so every launch takes LE = 2 by default.
+constexpr int kNttSmallTile = 1024;             // words per tile of a few-row launch (SFHE_NTT_T1K_ROWS, nttRows)
+// LE = stages per register round (2^LE words per thread, tile >> LE threads),
+// fixed by the launch's row count: below kNttSmallRows rows LE = 2 (twice the
+// waves per tile), from there on LE = 3 (fewer rounds and barriers).  Measured
+// on the sort (N=256 @ 2^16): thresholds 6 / 12 / 24 / 36 / all rows gave 64.6 /
+// 63.8 / 63.3 / 62.5 / 62.2 ms, so the threshold sits above every launch of the
+// sort.
 #ifndef SFHE_NTT_SMALL_ROWS
 #define SFHE_NTT_SMALL_ROWS 4096
 #endif
@@ -568,9 +570,6 @@ __device__ __forceinline__ void nttRound(u64* s, const NttTile& T, uint32_t S0, 
 template <bool INV, bool COL, int LE, int TILE>
 __device__ __forceinline__ void nttRoundDyn(int b, u64* s, const NttTile& T, uint32_t S0, uint32_t k0,
                                             u64 q, const u64* w, const u64* wS) {
-    if constexpr (LE >= 4) {
-        if (b == 4) return nttRound<INV, COL, LE, 4, TILE>(s, T, S0, k0, q, w, wS);
-    }
     if constexpr (LE >= 3) {
         if (b == 3) return nttRound<INV, COL, LE, 3, TILE>(s, T, S0, k0, q, w, wS);
     }
@@ -708,9 +707,6 @@ __device__ __forceinline__ void nttRoundFP(double* s, const NttTile& T, uint32_t
 template <bool INV, bool COL, int LE, int TILE>
 __device__ __forceinline__ void nttRoundDynFP(int b, double* s, const NttTile& T, uint32_t S0, uint32_t k0,
                                               double q, const double* w, double qinv) {
-    if constexpr (LE >= 4) {
-        if (b == 4) return nttRoundFP<INV, COL, LE, 4, TILE>(s, T, S0, k0, q, w, qinv);
-    }
     if constexpr (LE >= 3) {
         if (b == 3) return nttRoundFP<INV, COL, LE, 3, TILE>(s, T, S0, k0, q, w, qinv);
     }
@@ -836,15 +832,7 @@ struct RowGroup {
     // forward pass's first half otherwise uses: copy = the K source (P) rows
     // of polynomial p, coefficient form; pre = its dropped row l (with rescale)
     const struct MdColArgs* md;
-    // icol (k_ntt<false, true, ..., ICOL>, with lift): src is the dropped row
-    // after only the FIRST pass of its inverse NTT (the ROW pass); the forward
-    // COL pass runs the inverse COL pass of that tile (prime liftPrime,
-    // inverse twiddles iTw / iTwS / iTwD, n^-1) in its prologue, then lifts:
-    // a rescale's dropped row never makes the inverse COL round trip
-    uint32_t icol;
     uint32_t esumNeg;
-    const u64 *iTw, *iTwS;
-    const double* iTwD;
 };
 
 // Merged launches (stacked regions, batched ops; sfp_stack_begin /
@@ -905,7 +893,7 @@ __device__ unsigned long long g_mdrsTrace[kTraceSlots][8];  // k_mdrsf (FP64 blo
 #define NTT_MARK(i)
 #endif
 
-template <bool INV, bool COL, int LE, int TILE, int NG = 1, bool CONV = false, bool ICOL = false>
+template <bool INV, bool COL, int LE, int TILE, int NG = 1, bool CONV = false>
 __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, const sf_barrett* __restrict__ bar,
                                                   const u64* __restrict__ tw, const u64* __restrict__ twS,
                                                   const u64* __restrict__ ninv,
@@ -917,8 +905,6 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
                                                   const double* __restrict__ rowD) {
     __shared__ u64 s[TILE];
     __shared__ u64 tW[COL ? kNttColTw : 1], tX[COL ? kNttColTw : 1];  // COL twiddles (value; Shoup for integer rows)
-    __shared__ u64 tWi[ICOL ? kNttColTw : 1], tXi[ICOL ? kNttColTw : 1];  // ICOL: the source row's inverse ones
-    static_assert(!ICOL || (!INV && COL && !CONV), "the inverse COL prologue feeds the forward COL pass");
 #ifdef SFHE_NTT_TRACE
     unsigned long long tprev = clock64(), tacc[6] = {0, 0, 0, 0, 0, 0};
 #endif
@@ -1056,22 +1042,6 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
             cwD[c] = gwD[e];
         }
     }
-    // ICOL: the source row's prime and its inverse COL-pass twiddles, in
-    // flight with the tile and the forward ones
-    const uint32_t lp = ICOL ? G.liftPrime : 0u;
-    u64 icI[ICOL ? kColPer : 1], icX[ICOL ? kColPer : 1], icD[ICOL ? kColPer : 1];
-    if constexpr (ICOL) {
-        const u64* iI = G.iTw + (size_t)lp * n;
-        const u64* iX = G.iTwS + (size_t)lp * n;
-        const u64* iD = reinterpret_cast<const u64*>(G.iTwD) + (size_t)lp * n;
-#pragma unroll
-        for (int c = 0; c < kColPer; ++c) {
-            const uint32_t e = min(threadIdx.x + c * NT, colTw - 1) + 1;
-            icI[c] = iI[e];
-            icX[c] = iX[e];
-            icD[c] = iD[e];
-        }
-    }
     // ROW pass, FP64 rows, one group per thread per round (LE = 2): every
     // round's twiddles are data-independent, so all 4 x 3 of them (as local
     // and row factors, rowTwIssue) are loaded here, in flight together with
@@ -1108,18 +1078,6 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
             }
         }
     }
-    const u64 qL = ICOL ? bar[lp].q : 0;
-    const bool fpL = ICOL && useFp && qL < kFpPrimeBound;  // the source row's arithmetic
-    if constexpr (ICOL) {
-#pragma unroll
-        for (int c = 0; c < kColPer; ++c) {
-            const uint32_t e = threadIdx.x + c * NT;
-            if (e < colTw) {
-                tWi[e] = fpL ? icD[c] : icI[c];
-                if (!fpL) tXi[e] = icX[c];
-            }
-        }
-    }
     const u64* rw = COL ? tW : gw;
     const u64* rx = COL ? tX : gx;
     u64* cp = nullptr;
@@ -1133,11 +1091,6 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
         const uint32_t e = 2 * (threadIdx.x + k * NT);
         const size_t g = tileOff(k);
         ulonglong2 x = xr[k];
-        if constexpr (ICOL) {  // the source row as its own prime's pass stages it (lifted after its COL rounds)
-            s[ldsSw(e)] = fpL ? __double_as_longlong(u2d(x.x)) : x.x;
-            s[ldsSw(e + 1)] = fpL ? __double_as_longlong(u2d(x.y)) : x.y;
-            continue;
-        }
         if (FIRST) {
             if (cp) *reinterpret_cast<ulonglong2*>(cp + g) = x;
             if (pre) {
@@ -1168,44 +1121,6 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
     __syncthreads();
     NTT_MARK(0);
     const uint32_t nr = (T.d + LE - 1) / LE;
-    if constexpr (ICOL) {
-        // the source tile's inverse COL pass (k_ntt<true, true>'s rounds and
-        // its n^-1 store, canonical mod q_l) ...
-        const double qLd = (double)qL, qLi = qinvD[lp];
-        for (uint32_t ri = 0; ri < nr; ++ri) {
-            const uint32_t r = nr - 1 - ri;
-            const uint32_t k0 = LE * r;
-            const int b = (int)min((uint32_t)LE, T.d - k0);
-            if (fpL)
-                nttRoundDynFP<true, true, LE, TILE>(b, reinterpret_cast<double*>(s), T, 0u, k0, qLd,
-                                                    reinterpret_cast<const double*>(tWi), qLi);
-            else
-                nttRoundDyn<true, true, LE, TILE>(b, s, T, 0u, k0, qL, tWi, tXi);
-            __syncthreads();
-        }
-        // ... then, word by word (each thread its own slots), the centred lift
-        // to this row's prime that the unfused forward pass applies at its load
-        const u64 niL = ninv[lp], niLS = ninvS[lp];
-        const double niLD = ninvD[lp], niLQ = ninvQ[lp];
-#pragma unroll
-        for (int k = 0; k < NPAIR; ++k) {
-            const uint32_t e = 2 * (threadIdx.x + k * NT);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                u64 v = s[ldsSw(e + h)];
-                if (fpL) {
-                    v = d2u(fpReduce(fpMulMod(__longlong_as_double(v), niLD, niLQ, qLd), qLd, qLi));
-                } else {
-                    v = sf_mul_shoup_lazy(v, niL, niLS, qL);
-                    v = v >= qL ? v - qL : v;
-                }
-                u64 rr = sf_reduce128(v, 0, &LB);
-                if (v > lhalf) rr = sf_sub(rr, lsub, q);
-                s[ldsSw(e + h)] = fp ? __double_as_longlong(u2d(rr)) : rr;
-            }
-        }
-        __syncthreads();
-    }
     if constexpr (kPfBuild) {
         if (rowPf) {
 #pragma unroll
@@ -4763,31 +4678,6 @@ static int nttFp() {
     return on;
 }
 
-// SFHE_NTT_SMALL_TILE (512 / 1024) and SFHE_NTT_SMALL_LE (2 / 3): the
-// small-launch tile and register-round width (A/B knobs; defaults measured);
-// SFHE_NTT_LE: register-round width experiments for big launches (2, 3, 4)
-static uint32_t nttSmallTile() {
-    static const uint32_t v = [] {
-        const char* e = std::getenv("SFHE_NTT_SMALL_TILE");
-        return e ? (uint32_t)std::atoi(e) : 1024u;
-    }();
-    return v;
-}
-static int nttSmallLe() {
-    static const int v = [] {
-        const char* e = std::getenv("SFHE_NTT_SMALL_LE");
-        return e ? std::atoi(e) : 2;
-    }();
-    return v;
-}
-static int nttLe() {
-    static const int v = [] {
-        const char* e = std::getenv("SFHE_NTT_LE");
-        return e ? std::atoi(e) : 0;
-    }();
-    return v;
-}
-
 static RowGroup rowsOf(uint32_t P, uint32_t R, sfp_limbs pm) {
     RowGroup G;
     std::memset(&G, 0, sizeof G);
@@ -4797,29 +4687,6 @@ static RowGroup rowsOf(uint32_t P, uint32_t R, sfp_limbs pm) {
     return G;
 }
 
-// Would a forward NTT over `rows` rows take a two-stage (LE = 2) COL pass --
-// the passes that have the inverse-COL prologue (RowGroup::icol)?  Mirrors
-// nttRows' choice of path.  Off by default (SFHE_ICOL=1 turns it on).
-static int nttLe();
-static uint32_t nttSmallTile();
-static int nttSmallLe();
-static uint32_t nttT1kRows();
-static bool icolPath(sfp_dev* d, uint32_t rows) {
-    static const bool on = [] {  // (measured: sort 36.22 -> 36.63 ms with it on)
-        const char* v = std::getenv("SFHE_ICOL");
-        return v && *v == '1';
-    }();
-    if (!on || d->n <= (uint32_t)kNttTile) return false;
-    const uint32_t st = nttSmallTile();
-    const bool t1k = rows <= nttT1kRows() && d->n <= st * 128u;
-    if (t1k) return nttSmallLe() == 2 && (st == 1024 || st == 512);
-    const int le = nttLe();
-    return (le ? le : (rows < (uint32_t)kNttSmallRows ? 2 : 3)) == 2;
-}
-
-// Both passes of a (batched) NTT over the rows of G -- or only the first
-// (passes == 1: its output feeds a fused second pass, k_ntt_ks) or only the
-// second (passes == 2: a fused kernel ran the first).
 static uint32_t nttT1kRows() {
     static const uint32_t v = [] {
         const char* e = std::getenv("SFHE_NTT_T1K_ROWS");
@@ -4827,7 +4694,10 @@ static uint32_t nttT1kRows() {
     }();
     return v;
 }
-static int nttFp();
+
+// Both passes of a (batched) NTT over the rows of G -- or only the first
+// (passes == 1: its output feeds a fused second pass, k_ntt_ks) or only the
+// second (passes == 2: a fused kernel ran the first).
 static void nttRows(sfp_dev* d, const RowGroup& G0, int inverse, int passes = 3) {
     const RowGroup& G = G0;
     const uint32_t rows = G.P * G.R;
@@ -4860,13 +4730,9 @@ static void nttRows(sfp_dev* d, const RowGroup& G0, int inverse, int passes = 3)
     // 64) they run 1024-word tiles -- twice the blocks, half the work each;
     // needs >= 2 columns per COL tile, i.e. n <= 2^17.  Measured on the metric
     // sort: NTT 47.9 -> 46.0 ms, wall 58.1 -> 57.5 ms.
-    const uint32_t t1kRows = nttT1kRows();
-    const uint32_t smallTile = nttSmallTile();
-    const int smallLe = nttSmallLe();
-    const bool t1k = rows <= t1kRows && d->n <= smallTile * 128u;
-    dim3 g(d->n / (t1k ? smallTile : (uint32_t)kNttTile), rows);
+    const bool t1k = rows <= nttT1kRows() && d->n <= (uint32_t)kNttSmallTile * 128u;
+    dim3 g(d->n / (uint32_t)(t1k ? kNttSmallTile : kNttTile), rows);
     uint32_t gridRows = rows;  // (k_modup_col: grid rows are groups of target rows)
-    const bool small = rows < (uint32_t)kNttSmallRows;
     int npass = 0;
     // kern2 / kern4: the same pass over two / four row groups (merged launches), or null
     auto pass = [&](auto kern, NttKern2 kern2, NttKern4 kern4, NttKern8 kern8, int threads) {
@@ -4903,134 +4769,69 @@ static void nttRows(sfp_dev* d, const RowGroup& G0, int inverse, int passes = 3)
             issueRec(d, std::move(r));
         });
     };
-    const int le = nttLe();
-    const int L = le ? le : (small ? 2 : 3);
-    constexpr int T = kNttTile;
-    auto smallPasses = [&](auto tileC) {
-        constexpr int ST = decltype(tileC)::value;
-        if (smallLe == 3) {
-            if (!inverse) {
-                pass(k_ntt<false, true, 3, ST>, NttKern2{}, NttKern4{}, NttKern8{}, ST >> 3);
-                pass(k_ntt<false, false, 3, ST>, NttKern2{}, NttKern4{}, NttKern8{}, ST >> 3);
-            } else {
-                pass(k_ntt<true, false, 3, ST>, NttKern2{}, NttKern4{}, NttKern8{}, ST >> 3);
-                pass(k_ntt<true, true, 3, ST>, NttKern2{}, NttKern4{}, NttKern8{}, ST >> 3);
-            }
-        } else if (!inverse) {
-            if (G.cy)  // ModUpPlan: the conversion in the COL pass's prologue (modupConvOk: LE 2, 1024-word tiles)
-                pass(k_ntt<false, true, 2, ST, 1, true>, k_ntt<false, true, 2, ST, 2, true>,
-                     k_ntt<false, true, 2, ST, 4, true>, k_ntt<false, true, 2, ST, 8, true>, ST >> 2);
-            else if (G.icol)  // a rescale's lift with its source's inverse COL pass in the prologue
-                pass(k_ntt<false, true, 2, ST, 1, false, true>, k_ntt<false, true, 2, ST, 2, false, true>,
-                     k_ntt<false, true, 2, ST, 4, false, true>, k_ntt<false, true, 2, ST, 8, false, true>, ST >> 2);
-            else
-                pass(k_ntt<false, true, 2, ST>, k_ntt<false, true, 2, ST, 2>, k_ntt<false, true, 2, ST, 4>, k_ntt<false, true, 2, ST, 8>, ST >> 2);
-            pass(k_ntt<false, false, 2, ST>, k_ntt<false, false, 2, ST, 2>, k_ntt<false, false, 2, ST, 4>, k_ntt<false, false, 2, ST, 8>, ST >> 2);
-        } else {
-            pass(k_ntt<true, false, 2, ST>, k_ntt<true, false, 2, ST, 2>, k_ntt<true, false, 2, ST, 4>, k_ntt<true, false, 2, ST, 8>, ST >> 2);
-            pass(k_ntt<true, true, 2, ST>, k_ntt<true, true, 2, ST, 2>, k_ntt<true, true, 2, ST, 4>, k_ntt<true, true, 2, ST, 8>, ST >> 2);
-        }
-    };
-    if (G.icol && (inverse || !icolPath(d, rows))) {
-        record(d, "ntt: inverse-COL prologue outside its shape", hipErrorInvalidValue);
-        return;
-    }
+    const int L = rows < (uint32_t)kNttSmallRows ? 2 : 3;  // (see kNttSmallRows)
     static const bool modupCol = [] {  // SFHE_MODUP_COL=0: k_ntt<..., CONV> (one target per block; A/B)
         const char* v = std::getenv("SFHE_MODUP_COL");
         return !v || *v != '0';
     }();
-    if (G.md) {
-        // ModDown (mdColArgs): its conversion + the COL pass, kModdownTg targets per block
-        if (inverse || d->logn != 16 || smallTile != 1024 || L != 2 || passes != 3) {
-            record(d, "ntt: fused ModDown pass outside its shape", hipErrorInvalidValue);
+    // ModDown (mdColArgs): its conversion + the COL pass, kModdownTg targets per block
+    if (G.md && (inverse || d->logn != 16 || L != 2 || passes != 3)) {
+        record(d, "ntt: fused ModDown pass outside its shape", hipErrorInvalidValue);
+        return;
+    }
+    // ModUpPlan at ring 2^16: the conversion + COL pass, kModupTg targets per block
+    const bool modupColPass = G.cy && modupCol && !inverse && d->logn == 16 && L == 2;
+    // small launches (fewer than SFHE_MODUP_TG_SMALL blocks at kModupTg
+    // targets per block, default 512: two per CU) take two targets per
+    // block -- twice the blocks, half of each block's serial target chain
+    static const uint32_t tgSmall = [] {
+        const char* v = std::getenv("SFHE_MODUP_TG_SMALL");
+        return v ? (uint32_t)std::atoi(v) : 512u;
+    }();
+    // The LE = 2 pass pair at one tile size.  (Each specialisation is named in
+    // a call of its own: named only inside a conditional expression, the
+    // device code of some was never emitted -- "Cannot find Symbol" at launch.)
+    auto le2Passes = [&](auto tileC) {
+        constexpr int TL = decltype(tileC)::value;
+        constexpr int TH = TL >> 2;
+        if (inverse) {
+            pass(k_ntt<true, false, 2, TL>, k_ntt<true, false, 2, TL, 2>, k_ntt<true, false, 2, TL, 4>, k_ntt<true, false, 2, TL, 8>, TH);
+            pass(k_ntt<true, true, 2, TL>, k_ntt<true, true, 2, TL, 2>, k_ntt<true, true, 2, TL, 4>, k_ntt<true, true, 2, TL, 8>, TH);
             return;
         }
-        constexpr int TG = kModdownTg;
-        g.y = G.P * ((G.R + TG - 1) / TG);
-        gridRows = g.y;
-        if (t1k)
-            pass(k_moddown_col<1024, 1, TG>, k_moddown_col<1024, 2, TG>, k_moddown_col<1024, 4, TG>,
-                 k_moddown_col<1024, 8, TG>, 1024 >> 2);
-        else
-            pass(k_moddown_col<T, 1, TG>, k_moddown_col<T, 2, TG>, k_moddown_col<T, 4, TG>, k_moddown_col<T, 8, TG>,
-                 T >> 2);
-        g.y = rows;
-        gridRows = rows;
-        if (t1k)
-            pass(k_ntt<false, false, 2, 1024>, k_ntt<false, false, 2, 1024, 2>, k_ntt<false, false, 2, 1024, 4>,
-                 k_ntt<false, false, 2, 1024, 8>, 1024 >> 2);
-        else
-            pass(k_ntt<false, false, 2, T>, k_ntt<false, false, 2, T, 2>, k_ntt<false, false, 2, T, 4>,
-                 k_ntt<false, false, 2, T, 8>, T >> 2);
-    } else if (G.cy && modupCol && !inverse && d->logn == 16 && smallTile == 1024 && L == 2) {
-        // ModUpPlan at ring 2^16: the conversion + COL pass, kModupTg targets per block
-        // small launches (fewer than SFHE_MODUP_TG_SMALL blocks at kModupTg
-        // targets per block, default 512: two per CU) take two targets per
-        // block -- twice the blocks, half of each block's serial target chain
-        constexpr int TG = kModupTg;
-        static const uint32_t tgSmall = [] {
-            const char* v = std::getenv("SFHE_MODUP_TG_SMALL");
-            return v ? (uint32_t)std::atoi(v) : 512u;
-        }();
-        const bool tg2 = G.P * ((G.R + TG - 1) / TG) * g.x < tgSmall;
-        const int tg = tg2 ? 2 : TG;
-        g.y = G.P * ((G.R + tg - 1) / tg);
-        gridRows = g.y;
-        // (each specialisation named in a call of its own: named only inside a
-        // conditional expression, the device code of some was never emitted --
-        // "Cannot find Symbol" at launch)
-        if (t1k && tg2)
-            pass(k_modup_col<1024, 1, 2>, k_modup_col<1024, 2, 2>, k_modup_col<1024, 4, 2>, k_modup_col<1024, 8, 2>,
-                 1024 >> 2);
-        else if (t1k)
-            pass(k_modup_col<1024, 1, TG>, k_modup_col<1024, 2, TG>, k_modup_col<1024, 4, TG>, k_modup_col<1024, 8, TG>,
-                 1024 >> 2);
-        else if (tg2)
-            pass(k_modup_col<T, 1, 2>, k_modup_col<T, 2, 2>, k_modup_col<T, 4, 2>, k_modup_col<T, 8, 2>, T >> 2);
-        else
-            pass(k_modup_col<T, 1, TG>, k_modup_col<T, 2, TG>, k_modup_col<T, 4, TG>, k_modup_col<T, 8, TG>, T >> 2);
-        g.y = rows;
-        gridRows = rows;
-        if (t1k)
-            pass(k_ntt<false, false, 2, 1024>, k_ntt<false, false, 2, 1024, 2>, k_ntt<false, false, 2, 1024, 4>,
-                 k_ntt<false, false, 2, 1024, 8>, 1024 >> 2);
-        else
-            pass(k_ntt<false, false, 2, T>, k_ntt<false, false, 2, T, 2>, k_ntt<false, false, 2, T, 4>,
-                 k_ntt<false, false, 2, T, 8>, T >> 2);
-    } else if (t1k) {
-        if (smallTile == 512)
-            smallPasses(std::integral_constant<int, 512>{});
-        else
-            smallPasses(std::integral_constant<int, 1024>{});
-    } else if (!inverse) {
-        if (L == 4) {
-            pass(k_ntt<false, true, 4, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 4);
-            pass(k_ntt<false, false, 4, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 4);
-        } else if (L == 2) {
-            if (G.cy)
-                pass(k_ntt<false, true, 2, T, 1, true>, k_ntt<false, true, 2, T, 2, true>,
-                     k_ntt<false, true, 2, T, 4, true>, k_ntt<false, true, 2, T, 8, true>, T >> 2);
-            else if (G.icol)
-                pass(k_ntt<false, true, 2, T, 1, false, true>, k_ntt<false, true, 2, T, 2, false, true>,
-                     k_ntt<false, true, 2, T, 4, false, true>, k_ntt<false, true, 2, T, 8, false, true>, T >> 2);
+        if (G.md) {
+            constexpr int TG = kModdownTg;
+            g.y = gridRows = G.P * ((G.R + TG - 1) / TG);
+            pass(k_moddown_col<TL, 1, TG>, k_moddown_col<TL, 2, TG>, k_moddown_col<TL, 4, TG>, k_moddown_col<TL, 8, TG>, TH);
+        } else if (modupColPass) {
+            constexpr int TG = kModupTg;
+            const bool tg2 = G.P * ((G.R + TG - 1) / TG) * g.x < tgSmall;
+            const int tg = tg2 ? 2 : TG;
+            g.y = gridRows = G.P * ((G.R + tg - 1) / tg);
+            if (tg2)
+                pass(k_modup_col<TL, 1, 2>, k_modup_col<TL, 2, 2>, k_modup_col<TL, 4, 2>, k_modup_col<TL, 8, 2>, TH);
             else
-                pass(k_ntt<false, true, 2, T>, k_ntt<false, true, 2, T, 2>, k_ntt<false, true, 2, T, 4>, k_ntt<false, true, 2, T, 8>, T >> 2);
-            pass(k_ntt<false, false, 2, T>, k_ntt<false, false, 2, T, 2>, k_ntt<false, false, 2, T, 4>, k_ntt<false, false, 2, T, 8>, T >> 2);
+                pass(k_modup_col<TL, 1, TG>, k_modup_col<TL, 2, TG>, k_modup_col<TL, 4, TG>, k_modup_col<TL, 8, TG>, TH);
+        } else if (G.cy) {  // ModUpPlan: the conversion in the COL pass's prologue, one target per block
+            pass(k_ntt<false, true, 2, TL, 1, true>, k_ntt<false, true, 2, TL, 2, true>,
+                 k_ntt<false, true, 2, TL, 4, true>, k_ntt<false, true, 2, TL, 8, true>, TH);
         } else {
-            pass(k_ntt<false, true, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
-            pass(k_ntt<false, false, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
+            pass(k_ntt<false, true, 2, TL>, k_ntt<false, true, 2, TL, 2>, k_ntt<false, true, 2, TL, 4>, k_ntt<false, true, 2, TL, 8>, TH);
         }
+        g.y = gridRows = rows;
+        pass(k_ntt<false, false, 2, TL>, k_ntt<false, false, 2, TL, 2>, k_ntt<false, false, 2, TL, 4>, k_ntt<false, false, 2, TL, 8>, TH);
+    };
+    constexpr int T = kNttTile;
+    if (t1k) {
+        le2Passes(std::integral_constant<int, kNttSmallTile>{});
+    } else if (L == 2) {
+        le2Passes(std::integral_constant<int, T>{});
+    } else if (!inverse) {  // kNttSmallRows rows or more: single-group LE = 3 kernels
+        pass(k_ntt<false, true, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
+        pass(k_ntt<false, false, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
     } else {
-        if (L == 4) {
-            pass(k_ntt<true, false, 4, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 4);
-            pass(k_ntt<true, true, 4, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 4);
-        } else if (L == 2) {
-            pass(k_ntt<true, false, 2, T>, k_ntt<true, false, 2, T, 2>, k_ntt<true, false, 2, T, 4>, k_ntt<true, false, 2, T, 8>, T >> 2);
-            pass(k_ntt<true, true, 2, T>, k_ntt<true, true, 2, T, 2>, k_ntt<true, true, 2, T, 4>, k_ntt<true, true, 2, T, 8>, T >> 2);
-        } else {
-            pass(k_ntt<true, false, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
-            pass(k_ntt<true, true, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
-        }
+        pass(k_ntt<true, false, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
+        pass(k_ntt<true, true, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
     }
     checkLaunch(d, "ntt");
 }
@@ -5209,42 +5010,25 @@ static uint32_t kernelFamily(const void* f) {
                               (const void*)k_ntt<false, true, 2, kNttTile, 2, true>,
                               (const void*)k_ntt<false, true, 2, kNttTile, 4, true>,
                               (const void*)k_ntt<false, true, 2, kNttTile, 8, true>,
-                              (const void*)k_ntt<false, true, 2, 1024, 1, true>, (const void*)k_ntt<false, true, 2, 1024, 2, true>,
-                              (const void*)k_ntt<false, true, 2, 1024, 4, true>, (const void*)k_ntt<false, true, 2, 1024, 8, true>})
+                              (const void*)k_ntt<false, true, 2, kNttSmallTile, 1, true>, (const void*)k_ntt<false, true, 2, kNttSmallTile, 2, true>,
+                              (const void*)k_ntt<false, true, 2, kNttSmallTile, 4, true>, (const void*)k_ntt<false, true, 2, kNttSmallTile, 8, true>})
             m[k] = SFP_FAM_NTT;  // (the ModUp COL pass with its conversion)
-        for (const void* k : {(const void*)k_ntt<false, true, 2, kNttTile, 1, false, true>,
-                              (const void*)k_ntt<false, true, 2, kNttTile, 2, false, true>,
-                              (const void*)k_ntt<false, true, 2, kNttTile, 4, false, true>,
-                              (const void*)k_ntt<false, true, 2, kNttTile, 8, false, true>,
-                              (const void*)k_ntt<false, true, 2, 1024, 1, false, true>,
-                              (const void*)k_ntt<false, true, 2, 1024, 2, false, true>,
-                              (const void*)k_ntt<false, true, 2, 1024, 4, false, true>,
-                              (const void*)k_ntt<false, true, 2, 1024, 8, false, true>,
-                              (const void*)k_ntt<false, true, 2, 512, 1, false, true>,
-                              (const void*)k_ntt<false, true, 2, 512, 2, false, true>,
-                              (const void*)k_ntt<false, true, 2, 512, 4, false, true>,
-                              (const void*)k_ntt<false, true, 2, 512, 8, false, true>})
-            m[k] = SFP_FAM_NTT;  // (a rescale's lift pass with its source's inverse COL pass: a row's read + write)
         for (const void* k : {(const void*)k_modup_col<kNttTile, 1, kModupTg>, (const void*)k_modup_col<kNttTile, 2, kModupTg>,
                               (const void*)k_modup_col<kNttTile, 4, kModupTg>, (const void*)k_modup_col<kNttTile, 8, kModupTg>,
-                              (const void*)k_modup_col<1024, 1, kModupTg>, (const void*)k_modup_col<1024, 2, kModupTg>,
-                              (const void*)k_modup_col<1024, 4, kModupTg>, (const void*)k_modup_col<1024, 8, kModupTg>,
+                              (const void*)k_modup_col<kNttSmallTile, 1, kModupTg>, (const void*)k_modup_col<kNttSmallTile, 2, kModupTg>,
+                              (const void*)k_modup_col<kNttSmallTile, 4, kModupTg>, (const void*)k_modup_col<kNttSmallTile, 8, kModupTg>,
                               (const void*)k_modup_col<kNttTile, 1, 2>, (const void*)k_modup_col<kNttTile, 2, 2>,
                               (const void*)k_modup_col<kNttTile, 4, 2>, (const void*)k_modup_col<kNttTile, 8, 2>,
-                              (const void*)k_modup_col<1024, 1, 2>, (const void*)k_modup_col<1024, 2, 2>,
-                              (const void*)k_modup_col<1024, 4, 2>, (const void*)k_modup_col<1024, 8, 2>})
+                              (const void*)k_modup_col<kNttSmallTile, 1, 2>, (const void*)k_modup_col<kNttSmallTile, 2, 2>,
+                              (const void*)k_modup_col<kNttSmallTile, 4, 2>, (const void*)k_modup_col<kNttSmallTile, 8, 2>})
             m[k] = SFP_FAM_NTT;
         for (const void* k : {(const void*)k_moddown_col<kNttTile, 1, kModdownTg>, (const void*)k_moddown_col<kNttTile, 2, kModdownTg>,
                               (const void*)k_moddown_col<kNttTile, 4, kModdownTg>, (const void*)k_moddown_col<kNttTile, 8, kModdownTg>,
-                              (const void*)k_moddown_col<1024, 1, kModdownTg>, (const void*)k_moddown_col<1024, 2, kModdownTg>,
-                              (const void*)k_moddown_col<1024, 4, kModdownTg>, (const void*)k_moddown_col<1024, 8, kModdownTg>})
+                              (const void*)k_moddown_col<kNttSmallTile, 1, kModdownTg>, (const void*)k_moddown_col<kNttSmallTile, 2, kModdownTg>,
+                              (const void*)k_moddown_col<kNttSmallTile, 4, kModdownTg>, (const void*)k_moddown_col<kNttSmallTile, 8, kModdownTg>})
             m[k] = SFP_FAM_NTT;
-        addNttAll<2, 1024>(m, true);
-        addNttAll<2, 512>(m, true);
+        addNttAll<2, kNttSmallTile>(m, true);
         addNttAll<3, kNttTile>(m, false);
-        addNttAll<4, kNttTile>(m, false);
-        addNttAll<3, 1024>(m, false);
-        addNttAll<3, 512>(m, false);
         for (const void* k : {(const void*)k_convf<13>, (const void*)k_convf<16>, (const void*)k_convf<kMaxConvSrc>,
                               (const void*)k_conv, (const void*)k_mdrsf<13, true>, (const void*)k_mdrsf<16, true>,
                               (const void*)k_mdrsf<kMaxConvSrc, true>, (const void*)k_mdrsf<13>,
@@ -5283,9 +5067,9 @@ static double fusedColRows(const void* arg, bool moddown) {
 template <int NG>
 static bool isFusedCol(const void* f, bool md) {
     return md ? (f == (const void*)k_moddown_col<kNttTile, NG, kModdownTg> ||
-                 f == (const void*)k_moddown_col<1024, NG, kModdownTg>)
-              : (f == (const void*)k_modup_col<kNttTile, NG, kModupTg> || f == (const void*)k_modup_col<1024, NG, kModupTg> ||
-                 f == (const void*)k_modup_col<kNttTile, NG, 2> || f == (const void*)k_modup_col<1024, NG, 2>);
+                 f == (const void*)k_moddown_col<kNttSmallTile, NG, kModdownTg>)
+              : (f == (const void*)k_modup_col<kNttTile, NG, kModupTg> || f == (const void*)k_modup_col<kNttSmallTile, NG, kModupTg> ||
+                 f == (const void*)k_modup_col<kNttTile, NG, 2> || f == (const void*)k_modup_col<kNttSmallTile, NG, 2>);
 }
 static double nttNodeRows(const hipKernelNodeParams& kp) {
     const void* f = kp.func;
@@ -5654,20 +5438,11 @@ static void rescaleCore(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t 
         A.preK = dmk + 2 * cnt;
         A.preKS = dmk + 2 * cnt + 1;
     }
-    // the dropped row's inverse COL pass runs in the lift pass's prologue
-    // (icol) where that pass has one: one dependent launch fewer per rescale
-    const bool icol = icolPath(d, npoly * cnt);
-    nttRows(d, A, 1, icol ? 1 : 3);
+    nttRows(d, A, 1);
     RowGroup B = rowsOf(npoly, cnt, sfp_limbs{cnt, cnt, 0, 0});
     B.src = RowPtr{last, (long long)n, 0};
     B.lift = 1;
     B.liftPrime = dropPrime;
-    if (icol) {
-        B.icol = 1;
-        B.iTw = d->ipsi;
-        B.iTwS = d->ipsiS;
-        B.iTwD = d->ipsiD;
-    }
     B.dst = RowPtr{tmp, (long long)cnt * n, (long long)n};
     B.epi = 1;
     B.ein = RowPtr{in, (long long)inStride, (long long)n};
@@ -5981,9 +5756,7 @@ static bool modupFuseOn() {  // SFHE_MODUP_FUSE=0: k_convf + the plain COL pass 
 }
 static const ModUpPlan* modupPlan(sfp_dev* d, const sfp_conv* const* convs, uint32_t ell, uint32_t K,
                                   uint32_t alpha) {
-    if (!modupFuseOn() || !nttFp() || d->n <= (uint32_t)kNttTile || nttSmallLe() != 2 || nttSmallTile() != 1024 ||
-        (nttLe() != 0 && nttLe() != 2))
-        return nullptr;
+    if (!modupFuseOn() || !nttFp() || d->n <= (uint32_t)kNttTile) return nullptr;
     auto it = d->plans.find(convs[0]);
     if (it != d->plans.end()) return it->second;
     const uint32_t beta = (ell + alpha - 1) / alpha, rows = ell + K;
@@ -6325,8 +6098,8 @@ void sfp_ks_inner_mul_aut(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint
     checkLaunch(d, "ks_inner_mul");
 }
 
-// The fused ModDown COL pass (k_moddown_col): ring 2^16 with the default NTT
-// shape (LE 2, 1024-word small tiles), a ModDown table (every source FP64,
+// The fused ModDown COL pass (k_moddown_col): ring 2^16, fewer than
+// kNttSmallRows rows (LE 2), a ModDown table (every source FP64,
 // target t on prime t; sfp_upload_conv), with the rescale its dropped prime
 // FP64 too.  Returns the call's device table (constant arena), or null: the
 // unfused launches run.  Off by default (SFHE_MODDOWN_COL=1 turns it on): A/B
@@ -6344,8 +6117,7 @@ static bool moddownColOn() {
 // row l -> n^-1; its FP64 rows are stored as doubles.
 static const MdColArgs* mdColArgs(sfp_dev* d, const sfp_conv* c, uint32_t targets, bool rs, uint32_t l, uint32_t Lq,
                                   const u64* pmod, const u64* lsub, u64 pinvl, RowGroup& A) {
-    if (!moddownColOn() || !nttFp() || d->logn != 16 || nttSmallLe() != 2 || nttSmallTile() != 1024 ||
-        (nttLe() != 0 && nttLe() != 2) || c->mdState != 1 || c->ns > (uint32_t)kMaxConvSrc)
+    if (!moddownColOn() || !nttFp() || d->logn != 16 || c->mdState != 1 || c->ns > (uint32_t)kMaxConvSrc)
         return nullptr;
     static const uint32_t maxT = [] {  // SFHE_MODDOWN_COL_MAXT: fused up to this many target rows (A/B)
         const char* v = std::getenv("SFHE_MODDOWN_COL_MAXT");
