@@ -27,7 +27,8 @@ extern "C" {
 
 #define SFHE_ABI_VERSION 3  /* bumped when a declaration or struct below changes */
 /* (sfhe_decrypt_batch and sfhe_decode_counts were added at version 3: additions
- * only, no existing declaration changed, so the version stays) */
+ * only, no existing declaration changed, so the version stays; likewise
+ * sfhe_encrypt_batch and sfhe_sample_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -103,6 +104,11 @@ int sfhe_encode_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host);
  * and on the host since the last sfhe_op_stats reset (SFHE_DEV_DECODE=0, read
  * per call, decodes on the host; the results are bit-identical). */
 int sfhe_decode_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host);
+/* Small polynomials (an encryption's v, e0, e1; the keys' errors and secret)
+ * sampled on the device (sfp_sample_small) and on the host since the last
+ * sfhe_op_stats reset (SFHE_DEV_SAMPLE=0, read per call, samples on the host;
+ * the residues are identical). */
+int sfhe_sample_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host);
 /* Device memory held by the context's buffer pool (live and free blocks). */
 int sfhe_pool_bytes(sfhe_ctx* c, uint64_t* bytes);
 /* Engine contexts alive in this process (diagnostics: after every
@@ -143,6 +149,12 @@ int sfhe_comm_stats(sfhe_ctx* c, uint64_t* calls, double* bytes, double* ms);
  * (:14-33).  slots = 0 uses the batch size; level > 0 encrypts lower. */
 int sfhe_encrypt(sfhe_ctx* c, const double* values, size_t len, uint32_t slots, uint32_t level,
                  sfhe_ct** out);
+/* `count` inputs encrypted in one call: input k is the lens[k] values at
+ * values + k * stride (lens[k] <= stride), packed into `slots` slots (0: the
+ * batch size) at level levels[k] (levels NULL: level 0).  outs[k] equals what
+ * sfhe_encrypt gives when called on each input in order. */
+int sfhe_encrypt_batch(sfhe_ctx* c, const double* values, size_t stride, const size_t* lens, size_t count,
+                       uint32_t slots, const uint32_t* levels, sfhe_ct** outs);
 /* writes min(cap, slots) real parts; *len = slots */
 int sfhe_decrypt(sfhe_ctx* c, const sfhe_ct* ct, double* out, size_t cap, size_t* len);
 /* `count` ciphertexts (any mix of levels and slot counts) decrypted with one

@@ -292,6 +292,34 @@ int sfhe_encrypt(sfhe_ctx* c, const double* v, size_t len, uint32_t slots, uint3
     });
 }
 
+int sfhe_encrypt_batch(sfhe_ctx* c, const double* values, size_t stride, const size_t* lens, size_t count,
+                       uint32_t slots, const uint32_t* levels, sfhe_ct** outs) {
+    REQUIRE(c && (outs || !count) && (lens || !count), "null argument");
+    REQUIRE(c->keys.publicKey, "sfhe_keygen must be called first");
+    for (size_t k = 0; k < count; ++k) {
+        REQUIRE(lens[k] <= stride, "an input longer than the stride");
+        REQUIRE(values || !lens[k], "null values");
+    }
+    return guard([&] {
+        std::vector<Plaintext> pts(count);
+        for (size_t k = 0; k < count; ++k) {
+            const double* v = lens[k] ? values + k * stride : nullptr;
+            pts[k] = c->cc->MakeCKKSPackedPlaintext(std::vector<double>(v, v + lens[k]), 1, levels ? levels[k] : 0,
+                                                    nullptr, slots);
+        }
+        auto cts = c->cc->EncryptMany(c->keys.publicKey, pts);
+        for (size_t k = 0; k < count; ++k) outs[k] = wrap(cts[k]);
+    });
+}
+
+int sfhe_sample_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host) {
+    REQUIRE(c && device && host, "null argument");
+    auto s = c->cc->GetOpStats();
+    *device = s.dev_samples;
+    *host = s.host_samples;
+    return SFHE_OK;
+}
+
 int sfhe_decrypt(sfhe_ctx* c, const sfhe_ct* ct, double* out, size_t cap, size_t* len) {
     REQUIRE(c && ct, "null argument");
     REQUIRE(c->keys.secretKey, "no secret key");

@@ -1307,13 +1307,11 @@ class SfheInternal {
         auto key = s->alloc((size_t)digits * 2 * NP * n);
         key->ksTier = tier;
         auto tmp = s->alloc((size_t)NP * n);
-        std::vector<int64_t> e(n);
         for (uint32_t j = 0; j < digits; ++j) {
             uint64_t* b = key->ptr + (size_t)j * 2 * NP * n;
             uint64_t* a = b + (size_t)NP * n;
             sfp_sample_uniform(s->dev, a, all, s->nextSeed());
-            sampleCBD(s, e);
-            sfp_load_i64(s->dev, tmp->ptr, e.data(), all);
+            sampleErrorRows(s, tmp->ptr, all);
             sfp_ntt(s->dev, tmp->ptr, all, 0);
             // b = e - a s
             sfp_mul(s->dev, b, a, sk, all);
@@ -1344,6 +1342,40 @@ class SfheInternal {
             v[i] = (int64_t)(r % 3) - 1;
         }
     }
+
+    // Small polynomials (an encryption's v, e0, e1 and the keys' errors) are
+    // sampled on the device where the backend can (prims.h sfp_sample_small,
+    // sfp_encrypt_combine) unless SFHE_DEV_SAMPLE=0 (read per call: one process
+    // can compare the two paths) or a graph capture is open: seeds baked into
+    // a captured graph would repeat the randomness on every replay.
+    static bool deviceSample(const SfheContextState* s) {
+        if (!sfp_sample_small || !sfp_encrypt_combine || s->capturing) return false;
+        const char* v = std::getenv("SFHE_DEV_SAMPLE");
+        return !(v && *v == '0');
+    }
+
+    // one centred-binomial error polynomial into the coefficient-domain rows of
+    // m at dst (one nextSeed() either way: the same residues on both paths)
+    static void sampleErrorRows(SfheContextState* s, uint64_t* dst, sfp_limbs m) {
+        if (deviceSample(s)) {
+            const uint64_t seed = s->nextSeed();
+            const uint32_t kind = SFP_SMALL_CBD20;
+            sfp_sample_small(s->dev, dst, 0, 1, &seed, &kind, m);
+            s->stats.dev_samples++;
+            return;
+        }
+        std::vector<int64_t> e(s->n);
+        sampleCBD(s, e);
+        sfp_load_i64(s->dev, dst, e.data(), m);
+        s->stats.host_samples++;
+    }
+
+    // encryption (defined with CryptoContextImpl::Encrypt): one launch set covers
+    // at most kEncryptChunk ciphertexts and kEncryptTmpWords (128 MiB) of v, e0, e1
+    static constexpr size_t kEncryptChunk = 64, kEncryptTmpWords = (size_t)1 << 24;
+    static Ct encryptHostSample(CC* cc, const PublicKey<DCRTPoly>& pk, const Plaintext& pt);
+    static void encryptRows(CC* cc, const PublicKey<DCRTPoly>& pk, const std::vector<Plaintext>& pts,
+                            std::vector<Ct>& out);
 
     // device encoding of a plaintext at `level` with scale Delta_level
     // An encoding produced on another lane that may still be in flight is
@@ -2283,7 +2315,8 @@ KeyPair<DCRTPoly> CryptoContextImpl<DCRTPoly>::KeyGen() {
     }
     s->keyTag = sk->tag;
     std::vector<int64_t> tern(s->n);
-    SfheInternal::sampleTernary(s, tern);
+    SfheInternal::sampleTernary(s, tern);  // (on the host: sk->ternary keeps the host copy)
+    s->stats.host_samples++;
     sk->ternary.assign(tern.begin(), tern.end());
     const uint32_t NT = s->tablePrimes();
     sk->s = s->alloc((size_t)NT * s->n);
@@ -2300,9 +2333,7 @@ KeyPair<DCRTPoly> CryptoContextImpl<DCRTPoly>::KeyGen() {
     pk->a = s->alloc((size_t)R * s->n);
     pk->b = s->alloc((size_t)R * s->n);
     sfp_sample_uniform(s->dev, pk->a->ptr, q, s->nextSeed());
-    std::vector<int64_t> e(s->n);
-    SfheInternal::sampleCBD(s, e);
-    sfp_load_i64(s->dev, pk->b->ptr, e.data(), q);
+    SfheInternal::sampleErrorRows(s, pk->b->ptr, q);
     sfp_ntt(s->dev, pk->b->ptr, q, 0);
     auto t = s->alloc((size_t)R * s->n);
     sfp_mul(s->dev, t->ptr, pk->a->ptr, sk->s->ptr, SfheInternal::Q(s->Lq));
@@ -2395,23 +2426,16 @@ Plaintext CryptoContextImpl<DCRTPoly>::MakeCKKSPackedPlaintext(
     return std::make_shared<PlaintextImpl>(v, slots, level);
 }
 
-Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::Encrypt(const PublicKey<DCRTPoly>& pk,
-                                                         const Plaintext& pt) {
-    OpLock g(st.get());
-    SfheContextState* s = st.get();
-    if (!pk) SFHE_THROW("null public key");
-    if (s->sharded) {  // encrypt every row, keep this rank's
-        Ciphertext<DCRTPoly> full;
-        {
-            FullScope fs(s);
-            full = Encrypt(pk, pt);
-        }
-        return SfheInternal::localize(this, full);
-    }
+// One encryption with v, e0, e1 sampled on the host (the oracle's path, and the
+// product's with SFHE_DEV_SAMPLE=0 or inside a capture): each polynomial a
+// serial loop here, an upload that drains every lane, and an NTT of its own.
+Ciphertext<DCRTPoly> SfheInternal::encryptHostSample(CC* cc, const PublicKey<DCRTPoly>& pk, const Plaintext& pt) {
+    SfheContextState* s = cc->st.get();
     const uint32_t level = pt->level, ell = s->ellOf(level);
-    const sfp_limbs q = st->qmap(ell);
-    const uint64_t* m = SfheInternal::encoded(this, pt, level);
-    auto ct = SfheInternal::newCt(this, level, pt->slots);
+    const sfp_limbs q = s->qmap(ell);
+    const uint64_t* m = SfheInternal::encoded(cc, pt, level);
+    auto ct = SfheInternal::newCt(cc, level, pt->slots);
+    s->stats.host_samples += 3;
     // FLEXIBLEAUTOEXT: one extra row modulo q_ext (prime index extIdx)
     const uint32_t R = ell + (s->ext ? 1 : 0);
     const sfp_limbs qr{R, ell, s->extIdx, 0};
@@ -2434,7 +2458,7 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::Encrypt(const PublicKey<DCRTPo
         sfp_mul_add(s->dev, ct->c0, v, pk->b->ptr, e0, q);
         sfp_add(s->dev, ct->c0, ct->c0, m, q);
         sfp_mul_add(s->dev, ct->c1, v, pk->a->ptr, e1, q);
-        return SfheInternal::traced(this, ct, "Encrypt");
+        return SfheInternal::traced(cc, ct, "Encrypt");
     }
     // (v*pk + (e0 + q_ext*m, e1)) mod Q*q_ext; the q_ext row of q_ext*m is 0.
     // Dividing by q_ext leaves m at scale Delta_level with the encryption
@@ -2451,7 +2475,110 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::Encrypt(const PublicKey<DCRTPo
     sfp_mul_add(s->dev, c1x + qw, v + qw, pk->a->ptr + pkExt, e1 + qw, x1);
     sfp_rescale_ext(s->dev, ct->c0, c0x, R, s->extIdx, s->extInvModQ.data(), 2, rw,
                     (size_t)(ct->c1 - ct->c0));
-    return SfheInternal::traced(this, ct, "Encrypt");
+    return SfheInternal::traced(cc, ct, "Encrypt");
+}
+
+// out[k] = the encryption of pts[k] (every row: unsharded, or inside a
+// FullScope).  The seeds are drawn first, in list order, three per plaintext
+// (ternary, CBD, CBD) as sequential Encrypt calls draw them, so the batch is
+// residue for residue those calls and leaves seedCounter where they would.
+// Device sampling: the plaintexts are grouped by level; a group's 3 k small
+// polynomials are ONE sfp_sample_small and ONE batched forward NTT, its sums
+// ONE sfp_encrypt_combine (in place over e0 / e1 with the q_ext row, straight
+// into the ciphertexts without), then sfp_rescale_ext per ciphertext.  Nothing
+// here drains the device.
+void SfheInternal::encryptRows(CC* cc, const PublicKey<DCRTPoly>& pk, const std::vector<Plaintext>& pts,
+                               std::vector<Ct>& out) {
+    SfheContextState* s = cc->st.get();
+    out.assign(pts.size(), nullptr);
+    if (!deviceSample(s)) {
+        for (size_t k = 0; k < pts.size(); ++k) out[k] = encryptHostSample(cc, pk, pts[k]);
+        return;
+    }
+    std::vector<uint64_t> seeds(3 * pts.size());
+    for (auto& sd : seeds) sd = s->nextSeed();
+    std::map<uint32_t, std::vector<size_t>> groups;  // level -> indices
+    for (size_t k = 0; k < pts.size(); ++k) groups[pts[k]->level].push_back(k);
+    for (auto& g : groups) {
+        const uint32_t level = g.first, ell = s->ellOf(level);
+        // FLEXIBLEAUTOEXT: one extra row modulo q_ext (prime index extIdx)
+        const uint32_t R = ell + (s->ext ? 1 : 0);
+        const sfp_limbs qr{R, ell, s->extIdx, 0};
+        const size_t rw = (size_t)R * s->n;
+        // at most kEncryptChunk ciphertexts and kEncryptTmpWords of v, e0, e1 per launch
+        const size_t per = std::max<size_t>(1, std::min(kEncryptChunk, kEncryptTmpWords / (3 * rw)));
+        for (size_t k0 = 0; k0 < g.second.size(); k0 += per) {
+            const size_t cnt = std::min(per, g.second.size() - k0);
+            const size_t* idx = g.second.data() + k0;
+            std::vector<Plaintext> chunk;
+            for (size_t b = 0; b < cnt; ++b) chunk.push_back(pts[idx[b]]);
+            encodeBatch(cc, chunk, level);
+            auto tmp = s->alloc(3 * cnt * rw);
+            std::vector<uint64_t> sd;
+            std::vector<uint32_t> kinds;
+            for (size_t b = 0; b < cnt; ++b)
+                for (uint32_t j = 0; j < 3; ++j) {
+                    sd.push_back(seeds[3 * idx[b] + j]);
+                    kinds.push_back(j ? SFP_SMALL_CBD20 : SFP_SMALL_TERNARY);
+                }
+            sfp_sample_small(s->dev, tmp->ptr, rw, (uint32_t)(3 * cnt), sd.data(), kinds.data(), qr);
+            sfp_ntt_batch(s->dev, tmp->ptr, rw, (uint32_t)(3 * cnt), qr, 0);
+            s->stats.dev_samples += 3 * cnt;
+            std::vector<const uint64_t*> msg;
+            std::vector<uint64_t*> o0, o1;
+            for (size_t b = 0; b < cnt; ++b) {
+                const Plaintext& pt = pts[idx[b]];
+                msg.push_back(encoded(cc, pt, level));
+                auto ct = newCt(cc, level, pt->slots);
+                uint64_t* e0 = tmp->ptr + (3 * b + 1) * rw;
+                o0.push_back(s->ext ? e0 : ct->c0);
+                o1.push_back(s->ext ? e0 + rw : ct->c1);
+                out[idx[b]] = ct;
+            }
+            // (v*pk + (e0 + q_ext*m, e1)) mod Q*q_ext; the q_ext row of q_ext*m is 0.
+            // Dividing by q_ext leaves m at scale Delta_level with the encryption
+            // noise shrunk by q_ext (only the rounding of the division remains).
+            sfp_encrypt_combine(s->dev, tmp->ptr, rw, (uint32_t)cnt, msg.data(), o0.data(), o1.data(), pk->b->ptr,
+                                pk->a->ptr, s->Lq, ell, s->ext ? 1 : 0, s->extIdx, s->ext ? s->extModQ.data() : nullptr);
+            for (size_t b = 0; b < cnt; ++b) {
+                auto& ct = out[idx[b]];
+                if (s->ext)
+                    sfp_rescale_ext(s->dev, ct->c0, o0[b], R, s->extIdx, s->extInvModQ.data(), 2, rw,
+                                    (size_t)(ct->c1 - ct->c0));
+                traced(cc, ct, "Encrypt");
+            }
+        }
+    }
+}
+
+std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EncryptMany(const PublicKey<DCRTPoly>& pk,
+                                                                          const std::vector<Plaintext>& pts) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    if (!pk) SFHE_THROW("null public key");
+    for (const auto& pt : pts)
+        if (!pt) SFHE_THROW("null plaintext");
+    std::vector<Ciphertext<DCRTPoly>> out;
+    if (!s->sharded) {
+        SfheInternal::encryptRows(this, pk, pts, out);
+        return out;
+    }
+    // encrypt every row, keep this rank's (in list order, a chunk per scope:
+    // the scope holds its full-row encodings until it ends)
+    for (size_t k0 = 0; k0 < pts.size(); k0 += SfheInternal::kEncryptChunk) {
+        const size_t k1 = std::min(pts.size(), k0 + SfheInternal::kEncryptChunk);
+        std::vector<Ciphertext<DCRTPoly>> full;
+        {
+            FullScope fs(s);
+            SfheInternal::encryptRows(this, pk, std::vector<Plaintext>(pts.begin() + k0, pts.begin() + k1), full);
+        }
+        for (auto& ct : full) out.push_back(SfheInternal::localize(this, ct));
+    }
+    return out;
+}
+
+Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::Encrypt(const PublicKey<DCRTPoly>& pk, const Plaintext& pt) {
+    return EncryptMany(pk, {pt})[0];
 }
 
 namespace {

@@ -326,6 +326,13 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     Ciphertext<DCRTPoly> Encrypt(const Plaintext& pt, const PublicKey<DCRTPoly>& pk) {
         return Encrypt(pk, pt);
     }
+    // Engine extension: the encryptions of pts (any mix of levels and slot
+    // counts), residue for residue what Encrypt gives on each in list order (the
+    // sampling seeds are drawn in that order).  Where the backend samples on the
+    // device (prims.h sfp_sample_small, sfp_encrypt_combine) a level's
+    // plaintexts cost one sampling launch, one batched NTT and one combining
+    // launch, with no device drain; elsewhere it is a loop over Encrypt.
+    std::vector<Ciphertext<DCRTPoly>> EncryptMany(const PublicKey<DCRTPoly>& pk, const std::vector<Plaintext>& pts);
     void Decrypt(const PrivateKey<DCRTPoly>& sk, const Ciphertext<DCRTPoly>& ct, Plaintext* out);
     void Decrypt(const Ciphertext<DCRTPoly>& ct, const PrivateKey<DCRTPoly>& sk, Plaintext* out) {
         Decrypt(sk, ct, out);
@@ -613,6 +620,7 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
                  automorph = 0, ntt_limbs = 0, wsum_terms = 0;
         uint64_t dev_encodes = 0, host_encodes = 0;  // plaintext encodings on the device / host
         uint64_t dev_decodes = 0, host_decodes = 0;  // decrypted ciphertexts decoded on the device / host
+        uint64_t dev_samples = 0, host_samples = 0;  // small polynomials (ternary, error) sampled on the device / host
         double algo_bytes = 0.0;  // SURVEY.md §8(d) byte model
         uint64_t pool_bytes = 0;  // device memory held by the context's pool (live + free blocks)
     };
@@ -697,7 +705,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 6
+#define SFHE_FACADE_ABI_VERSION 7
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

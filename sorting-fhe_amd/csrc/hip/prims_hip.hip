@@ -3724,6 +3724,91 @@ __global__ __launch_bounds__(kThreads) void k_load_i64(u64* __restrict__ p, cons
     }
 }
 
+// Small polynomials sampled where they are used (sfp_sample_small): polynomial
+// blockIdx.y of `count`, its (seed, kind) pair at sk[2 y], its rows at
+// p + y * stride.  The value of coefficient x is the host samplers' function of
+// (seed, x) -- ternary (r % 3) - 1, or the centred binomial popcount(r & 0xFFFFF)
+// - popcount((r >> 20) & 0xFFFFF), r = smix(seed + x) -- computed once and
+// stored to every row as k_load_i64 stores it: q - |v| for v < 0 (|v| <= 20 is
+// below every prime, so there is nothing to reduce).  Two coefficients per
+// thread, one 16-byte store per row; nothing is read but the row's prime.
+__global__ __launch_bounds__(kThreads) void k_sample_small(u64* __restrict__ p, size_t stride,
+                                                           const u64* __restrict__ sk, sfp_limbs m,
+                                                           const sf_barrett* __restrict__ bar, uint32_t logn) {
+    const uint32_t pairs = 1u << (logn - 1);
+    const u64 seed = sk[2 * blockIdx.y];
+    const bool cbd = sk[2 * blockIdx.y + 1] != SFP_SMALL_TERNARY;
+    u64* __restrict__ base = p + (size_t)blockIdx.y * stride;
+    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < pairs; i += gridDim.x * kThreads) {
+        int v[2];
+        for (int h = 0; h < 2; ++h) {
+            const u64 r = smix(seed + 2 * (u64)i + h);
+            v[h] = cbd ? __popcll(r & 0xFFFFFull) - __popcll((r >> 20) & 0xFFFFFull) : (int)(r % 3) - 1;
+        }
+        for (uint32_t limb = 0; limb < m.count; ++limb) {
+            const u64 q = bar[primeOf(m, limb)].q;
+            ulonglong2 o;
+            o.x = v[0] < 0 ? q - (u64)(-v[0]) : (u64)v[0];
+            o.y = v[1] < 0 ? q - (u64)(-v[1]) : (u64)v[1];
+            reinterpret_cast<ulonglong2*>(base + ((size_t)limb << logn))[i] = o;
+        }
+    }
+}
+
+// The public-key encryption's sums in one launch (sfp_encrypt_combine), for
+// ciphertext blockIdx.y of `count`: its v, e0, e1 (evaluation domain, rows of
+// map m) at t + (3 y + {0, 1, 2}) * stride, its message rows and its two output
+// pointers at io[3 y ..].  Row i < ell: out0 = v b_i + e0 + k_i msg, out1 =
+// v a_i + e1; the row after them (the q_ext row, with hasExt) reads the key's
+// row pkExtRow and gets no message term.  hasExt == 0: k_i is 1 (msg is added
+// as it is).  out0 / out1 may be the e0 / e1 rows themselves (every word is
+// read by the thread that then writes it), so those are not __restrict__.
+struct EncIo {
+    const u64* msg;
+    u64 *out0, *out1;
+};
+__global__ __launch_bounds__(kThreads) void k_encrypt_combine(const u64* t, size_t stride, const EncIo* __restrict__ io,
+                                                              const u64* __restrict__ pkb,
+                                                              const u64* __restrict__ pka, uint32_t pkExtRow,
+                                                              uint32_t ell, uint32_t hasExt, sfp_limbs m,
+                                                              const ConstArgs k, const sf_barrett* __restrict__ bar,
+                                                              uint32_t logn) {
+    const EncIo I = io[blockIdx.y];
+    const u64* v = t + (size_t)blockIdx.y * 3 * stride;
+    const u64* e0 = v + stride;
+    const u64* e1 = e0 + stride;
+    const size_t pairs = ((size_t)m.count << logn) >> 1;
+    const size_t rowPairs = (size_t)1 << (logn - 1);
+    for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < pairs; i += (size_t)gridDim.x * kThreads) {
+        const uint32_t limb = (uint32_t)((2 * i) >> logn);
+        const sf_barrett B = loadBar(bar, primeOf(m, limb));
+        const u64 q = B.q;
+        // the key's row of this prime: row `limb`, or row pkExtRow for the q_ext row
+        const size_t ki = limb < ell ? i : (size_t)pkExtRow * rowPairs + (i - (size_t)limb * rowPairs);
+        const ulonglong2 x = reinterpret_cast<const ulonglong2*>(v)[i];
+        const ulonglong2 yb = reinterpret_cast<const ulonglong2*>(pkb)[ki];
+        const ulonglong2 ya = reinterpret_cast<const ulonglong2*>(pka)[ki];
+        const ulonglong2 z0 = reinterpret_cast<const ulonglong2*>(e0)[i];
+        const ulonglong2 z1 = reinterpret_cast<const ulonglong2*>(e1)[i];
+        ulonglong2 r0, r1;
+        r0.x = sf_add(bmul(x.x, yb.x, B), z0.x, q);
+        r0.y = sf_add(bmul(x.y, yb.y, B), z0.y, q);
+        r1.x = sf_add(bmul(x.x, ya.x, B), z1.x, q);
+        r1.y = sf_add(bmul(x.y, ya.y, B), z1.y, q);
+        if (limb < ell) {
+            ulonglong2 w = reinterpret_cast<const ulonglong2*>(I.msg)[i];
+            if (hasExt) {
+                w.x = bmul(w.x, k.k[limb], B);
+                w.y = bmul(w.y, k.k[limb], B);
+            }
+            r0.x = sf_add(r0.x, w.x, q);
+            r0.y = sf_add(r0.y, w.y, q);
+        }
+        reinterpret_cast<ulonglong2*>(I.out0)[i] = r0;
+        reinterpret_cast<ulonglong2*>(I.out1)[i] = r1;
+    }
+}
+
 // Plain copies run as kernels on the compute stream (never on the DMA
 // engines), so every byte movement is ordered with the arithmetic around it.
 __global__ __launch_bounds__(kThreads) void k_copy16(ulonglong2* __restrict__ dst,
@@ -6466,6 +6551,57 @@ void sfp_load_i64(sfp_dev* d, uint64_t* p, const int64_t* c, sfp_limbs m) {
     SFP_GO(k_load_i64, dim3(ewGrid(d->n)), dim3(kThreads), p,
                        (const int64_t*)d->bounce, m, d->bar, d->logn);
     checkLaunch(d, "load_i64");
+}
+
+// No bounce buffer and no drain: the seeds and kinds travel through the
+// argument ring, ordered on the current lane like every other prim.
+int sfp_sample_small(sfp_dev* d, uint64_t* p, size_t stride, uint32_t count, const uint64_t* seeds,
+                     const uint32_t* kinds, sfp_limbs m) {
+    if (!count || !m.count) return 0;
+    if (!limbsOk(d, m, "sample_small")) return 0;
+    if (count > 65535u || (count > 1 && stride < (size_t)m.count * d->n)) {
+        record(d, "sample_small (more than 65535 polynomials, or a stride below the rows)", hipErrorInvalidValue);
+        return 0;
+    }
+    std::vector<u64> sk(2 * (size_t)count);
+    for (uint32_t i = 0; i < count; ++i) {
+        if (kinds[i] != SFP_SMALL_TERNARY && kinds[i] != SFP_SMALL_CBD20) {
+            record(d, "sample_small (unknown kind)", hipErrorInvalidValue);
+            return 0;
+        }
+        sk[2 * i] = seeds[i];
+        sk[2 * i + 1] = kinds[i];
+    }
+    const u64* dsk = (const u64*)ringPut(d, sk.data(), sk.size() * 8);
+    if (!dsk) return 0;
+    SFP_GO(k_sample_small, dim3(gridFor(d->n / 2, kThreads), count), dim3(kThreads), p, stride, dsk, m, d->bar,
+                       d->logn);
+    checkLaunch(d, "sample_small");
+    return 0;
+}
+
+int sfp_encrypt_combine(sfp_dev* d, const uint64_t* t, size_t stride, uint32_t count, const uint64_t* const* msg,
+                        uint64_t* const* out0, uint64_t* const* out1, const uint64_t* pkb, const uint64_t* pka,
+                        uint32_t pk_ext_row, uint32_t ell, int ext, uint32_t ext_prime, const uint64_t* k) {
+    if (!count || !ell) return 0;
+    const uint32_t R = ell + (ext ? 1 : 0);
+    const sfp_limbs m{R, ell, ext_prime, 0};
+    if (!limbsOk(d, m, "encrypt_combine")) return 0;
+    if (count > 65535u || ell > SFP_MAX_LIMBS || stride < (size_t)R * d->n || (ext && !k)) {
+        record(d, "encrypt_combine (a bad batch, row count, stride or constant array)", hipErrorInvalidValue);
+        return 0;
+    }
+    ConstArgs ka;
+    if (ext) std::memcpy(ka.k, k, (size_t)ell * 8);
+    std::vector<EncIo> io(count);
+    for (uint32_t b = 0; b < count; ++b) io[b] = EncIo{msg[b], out0[b], out1[b]};
+    const EncIo* dio = (const EncIo*)ringPut(d, io.data(), io.size() * sizeof(EncIo));
+    if (!dio) return 0;
+    const size_t pairs = ((size_t)R * d->n) / 2;
+    SFP_GO(k_encrypt_combine, dim3(ewGrid(pairs), count), dim3(kThreads), t, stride, dio, pkb, pka, pk_ext_row,
+                       ell, (uint32_t)(ext ? 1 : 0), m, ka, d->bar, d->logn);
+    checkLaunch(d, "encrypt_combine");
+    return 0;
 }
 
 

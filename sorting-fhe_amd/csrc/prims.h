@@ -355,6 +355,40 @@ void sfp_sample_uniform(sfp_dev* d, uint64_t* p, sfp_limbs m, uint64_t seed);
 // Load signed coefficients (same for every limb) reduced mod each prime.
 void sfp_load_i64(sfp_dev* d, uint64_t* p, const int64_t* coeffs, sfp_limbs m);
 
+// ---- optional: small polynomials sampled on the device ---------------------------
+// `count` polynomials, polynomial j into the m.count coefficient-domain rows at
+// p + j * stride.  Coefficient i of polynomial j is a function of (seeds[j], i)
+// alone, r = splitmix64(seeds[j] + i):
+//   SFP_SMALL_TERNARY  (int64)(r % 3) - 1
+//   SFP_SMALL_CBD20    popcount(r & 0xFFFFF) - popcount((r >> 20) & 0xFFFFF)
+// (the host layer's sampleTernary / sampleCBD), stored in every row as
+// sfp_load_i64 stores that value: q - |v| for v < 0, v otherwise.  seeds and
+// kinds are host arrays; they travel through the argument ring, so the prim
+// has no host synchronisation (sfp_load_i64 drains every lane).  Weak like the
+// prims above: where its address is null (the C oracle) the host layer samples
+// on the host and loads.
+#define SFP_SMALL_TERNARY 0u
+#define SFP_SMALL_CBD20 1u
+SFP_OPTIONAL int sfp_sample_small(sfp_dev* d, uint64_t* p, size_t stride, uint32_t count, const uint64_t* seeds,
+                                  const uint32_t* kinds, sfp_limbs m);
+// The sums of `count` public-key encryptions at one limb count in one launch.
+// Ciphertext b has v, e0, e1 (evaluation domain; ell rows of primes 0 .. ell-1
+// and, with ext, one more row of prime ext_prime) at t + (3 b + {0, 1, 2}) *
+// stride, and its message's ell rows at msg[b].  pkb / pka: the public key's
+// rows, row i < ell for prime i and row pk_ext_row for ext_prime.
+//   ext:  out0[b] = v pkb + e0 + k_i msg on the ell rows (k: host array of ell
+//         residues, q_ext mod q_i) and v pkb + e0 on the ext row; out1[b] =
+//         v pka + e1 -- ell + 1 rows each, the input of sfp_rescale_ext
+//   else: out0[b] = v pkb + e0 + msg, out1[b] = v pka + e1 (ell rows; k unused)
+// out0[b] / out1[b] may be b's own e0 / e1 rows (in place).  The canonical
+// residues of the sfp_mul_add / sfp_mul_const / sfp_add sequence.  msg, out0
+// and out1 are host arrays of device pointers (argument ring: no host
+// synchronisation).  Weak, as sfp_sample_small.
+SFP_OPTIONAL int sfp_encrypt_combine(sfp_dev* d, const uint64_t* t, size_t stride, uint32_t count,
+                                     const uint64_t* const* msg, uint64_t* const* out0, uint64_t* const* out1,
+                                     const uint64_t* pkb, const uint64_t* pka, uint32_t pk_ext_row, uint32_t ell,
+                                     int ext, uint32_t ext_prime, const uint64_t* k);
+
 // ---- CKKS encoding on the device ------------------------------------------------
 // The host encoder's tables, uploaded once per device: rot[j] = 5^j mod 2n
 // (j < n/2) and ksi[k] = exp(2 pi i k / 2n) as (re, im) pairs (k <= 2n).

@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "sfhe_groups_rccl", "sfhe_groups_host", "sfhe_groups",
     "sfhe_encode_counts", "sfhe_bootstrap_graphs",
     "sfhe_decrypt_batch", "sfhe_decode_counts",
+    "sfhe_encrypt_batch", "sfhe_sample_counts",
 ]
 
 
@@ -168,6 +169,8 @@ _SIGS = {
     "sfhe_bootstrap_graphs": (C.c_int, [_VP, _PU64]),
     "sfhe_decrypt_batch": (C.c_int, [_VP, C.POINTER(_VP), _SZ, _PD, _SZ, _PSZ]),
     "sfhe_decode_counts": (C.c_int, [_VP, _PU64, _PU64]),
+    "sfhe_encrypt_batch": (C.c_int, [_VP, _PD, _SZ, _PSZ, _SZ, _U32, _PU32, C.POINTER(_VP)]),
+    "sfhe_sample_counts": (C.c_int, [_VP, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -425,6 +428,31 @@ class Engine:
     def encrypt(self, values: Sequence[float], slots: int = 0, level: int = 0) -> "Ct":
         a = _darr(values)
         return self._new(self.lib.sfhe_encrypt, self.ctx, a, len(values), slots, level)
+
+    def encrypt_batch(self, value_lists: Sequence[Sequence[float]], slots: int = 0, levels=None) -> list:
+        """[encrypt(v, slots, level) for v, level in zip(value_lists, levels)] in
+        one call (levels None: level 0 throughout): the same ciphertexts, with
+        the sampling, the NTTs and the sums of each level batched."""
+        lists = [list(v) for v in value_lists]
+        if not lists:
+            return []
+        if levels is not None and len(levels) != len(lists):
+            raise ValueError("levels must have one entry per input")
+        count, stride = len(lists), max(1, max(len(v) for v in lists))
+        buf = (C.c_double * (stride * count))()
+        for k, v in enumerate(lists):
+            buf[k * stride:k * stride + len(v)] = v
+        lens = (C.c_size_t * count)(*[len(v) for v in lists])
+        lv = (C.c_uint32 * count)(*[int(x) for x in levels]) if levels is not None else None
+        outs = (_VP * count)()
+        self._chk(self.lib.sfhe_encrypt_batch(self.ctx, buf, stride, lens, count, slots, lv, outs))
+        return [Ct(self, C.c_void_p(h)) for h in outs]
+
+    def sample_counts(self):
+        """(device, host) small polynomials sampled since the last op_stats reset."""
+        d, h = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_sample_counts(self.ctx, C.byref(d), C.byref(h)))
+        return d.value, h.value
 
     def decrypt(self, ct: "Ct") -> list:
         n = ct.slots  # (sfhe_decrypt writes min(cap, slots) values: decrypt once)
