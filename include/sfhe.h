@@ -28,7 +28,8 @@ extern "C" {
 #define SFHE_ABI_VERSION 3  /* bumped when a declaration or struct below changes */
 /* (sfhe_decrypt_batch and sfhe_decode_counts were added at version 3: additions
  * only, no existing declaration changed, so the version stays; likewise
- * sfhe_encrypt_batch and sfhe_sample_counts) */
+ * sfhe_encrypt_batch and sfhe_sample_counts, and sfhe_sorter_sort_stable,
+ * sfhe_sorter_rank_stable and sfhe_tie_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -104,6 +105,11 @@ int sfhe_encode_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host);
  * and on the host since the last sfhe_op_stats reset (SFHE_DEV_DECODE=0, read
  * per call, decodes on the host; the results are bit-identical). */
 int sfhe_decode_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host);
+/* Tie terms of the stable rank (one per batch of sfhe_sorter_rank_stable)
+ * whose tensor ran as one fused launch (sfp_tie_tensor) and as the composed
+ * generic prims since the last sfhe_op_stats reset (SFHE_TIE_FUSED=0, read
+ * per call, composes; the results are bit-identical). */
+int sfhe_tie_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
 /* Small polynomials (an encryption's v, e0, e1; the keys' errors and secret)
  * sampled on the device (sfp_sample_small) and on the host since the last
  * sfhe_op_stats reset (SFHE_DEV_SAMPLE=0, read per call, samples on the host;
@@ -232,6 +238,17 @@ int sfhe_sorter_sort(sfhe_sorter* s, sfhe_ct* in, int n, int dg, int df, sfhe_ct
 int sfhe_sorter_rank(sfhe_sorter* s, const sfhe_ct* in, int n, int dg, int df, sfhe_ct** out);
 /* DirectSort<N>::rotationIndexCheckN (sort_algo.h:658-750) */
 int sfhe_sorter_place(sfhe_sorter* s, const sfhe_ct* rank, sfhe_ct* in, sfhe_ct** out);
+/* Engine extensions (additions at ABI 3): the tie-aware stable rank sort.
+ * sfhe_sorter_rank_stable gives #{j : x_j < x_r} + #{j < r : x_j = x_r}, so
+ * inputs with duplicate values sort and equal values keep their input order
+ * (place(rank_stable(keys), payload) orders records by key).  Inputs must be
+ * equal or at least the sign configuration's resolution apart (1/N for the
+ * default configurations).  The rank consumes one level more than
+ * sfhe_sorter_rank: a context needs mult_depth = sfhe_direct_sort_params'
+ * depth + 1; with less, both return SFHE_ESCHEME and the message names the
+ * depth needed. */
+int sfhe_sorter_sort_stable(sfhe_sorter* s, sfhe_ct* in, int n, int dg, int df, sfhe_ct** out);
+int sfhe_sorter_rank_stable(sfhe_sorter* s, const sfhe_ct* in, int n, int dg, int df, sfhe_ct** out);
 /* Kernel / dependency nodes of the sorter's captured sort graph (engine
  * extension, no reference counterpart): sort() runs its first call of a shape
  * eagerly, captures the second into a hipGraph and replays it from then on

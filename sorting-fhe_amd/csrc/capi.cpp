@@ -97,6 +97,8 @@ struct SorterBase {
     virtual ~SorterBase() = default;
     virtual Ct sort(const Ct& in, SignConfig& cfg) = 0;
     virtual Ct rank(const Ct& in, SignConfig& cfg) = 0;
+    virtual Ct sortStable(const Ct& in, SignConfig& cfg) = 0;
+    virtual Ct rankStable(const Ct& in, SignConfig& cfg) = 0;
     virtual Ct place(const Ct& rank, const Ct& in) = 0;
     virtual Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) = 0;
     virtual Ct hybrid(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk, int variant) = 0;
@@ -124,6 +126,12 @@ struct Sorter : SorterBase {
     Ct sort(const Ct& in, SignConfig& cfg) override { return ds.sort(in, SignFunc::CompositeSign, cfg); }
     Ct rank(const Ct& in, SignConfig& cfg) override {
         return ds.constructRank(in, SignFunc::CompositeSign, cfg);
+    }
+    Ct sortStable(const Ct& in, SignConfig& cfg) override {
+        return ds.sortStable(in, SignFunc::CompositeSign, cfg);
+    }
+    Ct rankStable(const Ct& in, SignConfig& cfg) override {
+        return ds.constructRankStable(in, SignFunc::CompositeSign, cfg);
     }
     Ct place(const Ct& r, const Ct& in) override { return ds.rotationIndexCheckN(r, in); }
     Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) override {
@@ -359,6 +367,14 @@ int sfhe_decode_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host) {
     return SFHE_OK;
 }
 
+int sfhe_tie_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
+    REQUIRE(c && fused && composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *fused = s.tie_fused;
+    *composed = s.tie_composed;
+    return SFHE_OK;
+}
+
 void sfhe_ct_free(sfhe_ct* ct) { delete ct; }
 
 int sfhe_ct_clone(const sfhe_ct* ct, sfhe_ct** out) {
@@ -532,6 +548,23 @@ int sfhe_sorter_rank(sfhe_sorter* s, const sfhe_ct* in, int n, int dg, int df, s
     return guard([&] {
         auto cfg = cfgOf(n, dg, df);
         *out = wrap(s->impl->rank(in->ct, cfg));
+    });
+}
+
+int sfhe_sorter_sort_stable(sfhe_sorter* s, sfhe_ct* in, int n, int dg, int df, sfhe_ct** out) {
+    REQUIRE(s && in && out, "null argument");
+    return guard([&] {
+        Quiet q(s->ctx->quiet);
+        auto cfg = cfgOf(n, dg, df);
+        *out = wrap(s->impl->sortStable(in->ct, cfg));
+    });
+}
+
+int sfhe_sorter_rank_stable(sfhe_sorter* s, const sfhe_ct* in, int n, int dg, int df, sfhe_ct** out) {
+    REQUIRE(s && in && out, "null argument");
+    return guard([&] {
+        auto cfg = cfgOf(n, dg, df);
+        *out = wrap(s->impl->rankStable(in->ct, cfg));
     });
 }
 

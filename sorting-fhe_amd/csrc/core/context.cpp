@@ -1403,8 +1403,10 @@ class SfheInternal {
     // Coefficient-domain rows of pt's encoding at `level` for the rows of map
     // m; values whose scaled coefficients need more than 62 bits are encoded
     // at scale / 2^shift and the residues multiplied by 2^shift mod q_i.
+    // encScale: the encoding's scale (0: Delta_level).
     static void encodeRows(SfheContextState* s, const Plaintext& pt, uint32_t level, uint64_t* dst,
-                           sfp_limbs m, std::vector<int64_t>* keep = nullptr) {
+                           sfp_limbs m, std::vector<int64_t>* keep = nullptr, double encScale = 0.0) {
+        const double scale = encScale != 0.0 ? encScale : s->scale[level];
         // On the device (sfp_encode: the same FFT, bit for bit, no host
         // synchronisation) unless the values could need the encoder's 2^shift
         // range extension, or a trace wants the host coefficients.
@@ -1416,7 +1418,7 @@ class SfheInternal {
             real = real && c.imag() == 0.0;
         }
         const char* he = std::getenv("SFHE_HOST_ENCODE");
-        const bool host = (he && *he == '1') || keep || !(mx * s->scale[level] < 2.0e18) ||
+        const bool host = (he && *he == '1') || keep || !(mx * scale < 2.0e18) ||
                           (pt->slots & (pt->slots - 1)) || pt->values.size() > pt->slots;
         if (!host) {
             std::vector<double> v;
@@ -1426,7 +1428,7 @@ class SfheInternal {
                 if (!real) v.push_back(c.imag());
             }
             auto scr = s->alloc((size_t)2 * pt->slots);
-            sfp_encode(s->dev, dst, v.data(), (uint32_t)pt->values.size(), real ? 1 : 0, pt->slots, s->scale[level],
+            sfp_encode(s->dev, dst, v.data(), (uint32_t)pt->values.size(), real ? 1 : 0, pt->slots, scale,
                        m, scr->ptr);
             s->stats.dev_encodes++;
             return;
@@ -1434,7 +1436,7 @@ class SfheInternal {
         s->stats.host_encodes++;
         std::vector<int64_t> local;
         std::vector<int64_t>& coeffs = keep ? *keep : local;
-        const int shift = ckks_encode(pt->values, pt->slots, s->n, s->scale[level], coeffs);
+        const int shift = ckks_encode(pt->values, pt->slots, s->n, scale, coeffs);
         sfp_load_i64(s->dev, dst, coeffs.data(), m);
         if (shift) {
             std::vector<u64> k(m.count);
@@ -1666,6 +1668,38 @@ class SfheInternal {
         auto buf = s->alloc((size_t)m.count * s->n);
         encodeRows(s, pt, level, buf->ptr, m);
         sfp_ntt(s->dev, buf->ptr, m, 0);
+        buf->ready = sfp_event_record(s->dev);
+        buf->readyEpoch = s->capturing ? s->captureEpoch : 0;
+        pt->encoded[key] = buf;
+        return buf->ptr;
+    }
+
+    // pt over `level`'s local rows (evaluation domain) encoded at the NEXT
+    // level's scale (EvalTieTerm's weight: a product of three factors then
+    // lands on Delta_{level+2} exactly after its two rescales), cached on the
+    // plaintext beside its other encodings
+    static const uint64_t* encodedNextScale(CC* cc, const Plaintext& pt, uint32_t level) {
+        SfheContextState* s = cc->st.get();
+        std::lock_guard<std::mutex> g(pt->encMutex);
+        const uint32_t ell = s->ellOf(level);
+        if (s->fullScope) {  // every row, uncached (as encoded())
+            if (s->rows(ell) != ell) SFHE_THROW("internal: encoding scope");
+            auto buf = s->alloc(s->polyWords(level));
+            encodeRows(s, pt, level, buf->ptr, s->qmap(ell), nullptr, s->scale[level + 1]);
+            sfp_ntt(s->dev, buf->ptr, s->qmap(ell), 0);
+            s->scopeKeep.push_back(buf);
+            return buf->ptr;
+        }
+        const uint32_t key = level | 0x20000000u;
+        auto it = pt->encoded.find(key);
+        if (it != pt->encoded.end() && staleEnc(s, it->second)) {
+            pt->encoded.erase(it);
+            it = pt->encoded.end();
+        }
+        if (it != pt->encoded.end()) return ready(s, it->second.get());
+        auto buf = s->alloc(s->polyWords(level));
+        encodeRows(s, pt, level, buf->ptr, s->qmap(ell), nullptr, s->scale[level + 1]);
+        sfp_ntt(s->dev, buf->ptr, s->qmap(ell), 0);
         buf->ready = sfp_event_record(s->dev);
         buf->readyEpoch = s->capturing ? s->captureEpoch : 0;
         pt->encoded[key] = buf;
@@ -3092,6 +3126,50 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMult(const Ciphertext<DCRT
 
 Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalSquare(const Ciphertext<DCRTPoly>& a) {
     return EvalMult(a, a);
+}
+
+// The product stays lazy over its three factors: s at Delta_l, W encoded at
+// Delta_{l+1} over level l's limbs and k at Delta_l Delta_{l+1}, so the
+// tensor's scale is Delta_l^2 Delta_{l+1} = Delta_{l+1}^2 q_l and the two
+// rescales land on Delta_{l+2} exactly; the relinearisation's rounding is
+// divided by both dropped primes.
+Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalTieTerm(const Ciphertext<DCRTPoly>& a, const Plaintext& W,
+                                                             double k) {
+    OpLock g(st.get());
+    SfheInternal::deps(st.get(), {&a});
+    SfheContextState* s = st.get();
+    if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalTieTerm");
+    const uint32_t level = a->level, ell = s->ellOf(level);
+    if (ell < 3) SFHE_THROW("no levels left (the tie term consumes two levels)");
+    const uint32_t slots = std::max(a->slots, W->slots);
+    const uint64_t* w = SfheInternal::encodedNextScale(this, W, level);
+    const auto kr = SfheInternal::constResidues(s, k * a->scale * s->scale[level + 1], ell);
+    const size_t pw = s->polyWords(level);
+    const sfp_limbs m = s->qmap(ell);
+    auto t = s->alloc(3 * pw);
+    uint64_t* d0 = t->ptr;
+    uint64_t* d1 = d0 + pw;
+    uint64_t* d2 = d1 + pw;
+    const char* knob = std::getenv("SFHE_TIE_FUSED");  // (read per call: tests switch it)
+    const bool fused = sfp_tie_tensor && !(knob && *knob == '0') && !s->shardAt(ell) &&
+                       sfp_tie_tensor(s->dev, d0, d1, d2, a->c0, a->c1, w, kr.data(), m) == 0;
+    if (fused) {
+        s->stats.tie_fused++;
+    } else {  // the same integers from the generic prims: u = W s + k, then the tensor of s and u
+        auto u = s->alloc(2 * pw);
+        uint64_t* u0 = u->ptr;
+        uint64_t* u1 = u0 + pw;
+        sfp_mul(s->dev, u0, a->c0, w, m);
+        sfp_mul(s->dev, u1, a->c1, w, m);
+        sfp_add_const(s->dev, u0, u0, kr.data(), m);
+        sfp_tensor(s->dev, d0, d1, d2, a->c0, a->c1, u0, u1, m);
+        s->stats.tie_composed++;
+    }
+    s->stats.ptmult++;
+    s->stats.tensor++;
+    s->countBytes(12.0 * ell * s->n * 8);  // 5 l B (x plaintext) + 7 l B (tensor), SURVEY §8(d)
+    auto r = SfheInternal::relinRescale(this, d0, d1, d2, level, slots);
+    return SfheInternal::traced(this, SfheInternal::rescale(this, r->c0, r->c1, level + 1, slots), "EvalTieTerm");
 }
 
 std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultMany(

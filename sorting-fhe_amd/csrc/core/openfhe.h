@@ -382,6 +382,16 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         return EvalMult(a, b);
     }
     Ciphertext<DCRTPoly> EvalSquare(const Ciphertext<DCRTPoly>& a);
+    // Engine extension (the stable rank sort's tie-aware term):
+    // s (.) (W (.) s + k), relinearised, at s's level + 2 -- the value of
+    // EvalMult(s, EvalAdd(EvalMult(s, W), k)) with the product kept lazy over
+    // its three factors (two rescales at the end, the relinearisation before
+    // both).  The tensor is one launch where the backend has prims.h
+    // sfp_tie_tensor; elsewhere (the C oracle, SFHE_TIE_FUSED=0 -- read per
+    // call --, a level whose rows are dealt over ranks, or the prim declining)
+    // sfp_mul, sfp_add_const and sfp_tensor compose the same integers.
+    // OpStats tie_fused / tie_composed count the calls of each kind.
+    Ciphertext<DCRTPoly> EvalTieTerm(const Ciphertext<DCRTPoly>& s, const Plaintext& W, double k);
     // Engine extension: EvalMult(a_i, b_i) for independent pairs, each formed
     // canonically (rescaled: the values a lazy product takes when its
     // consumer needs the canonical form); pairs at one level run as batched
@@ -623,6 +633,7 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         uint64_t dev_samples = 0, host_samples = 0;  // small polynomials (ternary, error) sampled on the device / host
         double algo_bytes = 0.0;  // SURVEY.md §8(d) byte model
         uint64_t pool_bytes = 0;  // device memory held by the context's pool (live + free blocks)
+        uint64_t tie_fused = 0, tie_composed = 0;  // EvalTieTerm tensors in one launch / composed of generic prims
     };
     OpStats GetOpStats() const;
     void ResetOpStats();
@@ -705,7 +716,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 7
+#define SFHE_FACADE_ABI_VERSION 8
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

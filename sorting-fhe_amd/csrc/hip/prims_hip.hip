@@ -2089,6 +2089,49 @@ __global__ __launch_bounds__(kThreads) void k_tensor(u64* __restrict__ d0, u64* 
     }
 }
 
+// The tie-aware rank term's tensor (prims.h sfp_tie_tensor): the tensor of
+// (s0, s1) with (u0, u1) = (w s0 + k, w s1), u formed in registers -- three
+// rows read and three written per limb.  Every intermediate is the canonical
+// residue sfp_mul / sfp_add_const would have stored, so the outputs equal
+// k_tensor's on those.
+__global__ __launch_bounds__(kThreads) void k_tie_tensor(u64* __restrict__ d0, u64* __restrict__ d1,
+                                                         u64* __restrict__ d2, const u64* __restrict__ s0,
+                                                         const u64* __restrict__ s1, const u64* __restrict__ w,
+                                                         const ConstArgs k, sfp_limbs m,
+                                                         const sf_barrett* __restrict__ bar, uint32_t logn) {
+    // two coefficients per thread (16-byte loads and stores)
+    const size_t pairs = ((size_t)m.count << logn) >> 1;
+    for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < pairs;
+         i += (size_t)gridDim.x * kThreads) {
+        const uint32_t limb = (uint32_t)((2 * i) >> logn);
+        const sf_barrett B = loadBar(bar, primeOf(m, limb));
+        const u64 q = B.q, kk = k.k[limb];
+        const ulonglong2 x0 = reinterpret_cast<const ulonglong2*>(s0)[i];
+        const ulonglong2 x1 = reinterpret_cast<const ulonglong2*>(s1)[i];
+        const ulonglong2 y = reinterpret_cast<const ulonglong2*>(w)[i];
+        ulonglong2 u0, u1;
+        u0.x = sf_add(bmul(x0.x, y.x, B), kk, q);
+        u0.y = sf_add(bmul(x0.y, y.y, B), kk, q);
+        u1.x = bmul(x1.x, y.x, B);
+        u1.y = bmul(x1.y, y.y, B);
+        Acc t{0, 0}, u{0, 0};
+        macc(t, x0.x, u1.x);
+        macc(t, x1.x, u0.x);
+        macc(u, x0.y, u1.y);
+        macc(u, x1.y, u0.y);
+        ulonglong2 r0, r1, r2;
+        r0.x = bmul(x0.x, u0.x, B);
+        r0.y = bmul(x0.y, u0.y, B);
+        r1.x = sf_reduce128_acc(t.lo, t.hi, &B);
+        r1.y = sf_reduce128_acc(u.lo, u.hi, &B);
+        r2.x = bmul(x1.x, u1.x, B);
+        r2.y = bmul(x1.y, u1.y, B);
+        reinterpret_cast<ulonglong2*>(d0)[i] = r0;
+        reinterpret_cast<ulonglong2*>(d1)[i] = r1;
+        reinterpret_cast<ulonglong2*>(d2)[i] = r2;
+    }
+}
+
 struct PtrList {
     const u64* p[SFP_MAX_WSUM];
 };
@@ -5337,6 +5380,23 @@ void sfp_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const uint
     SFP_GO(k_tensor, dim3(ewGrid(total / 2)), dim3(kThreads), d0, d1, d2, a0, a1,
                        b0, b1, m, d->bar, d->logn);
     checkLaunch(d, "tensor");
+}
+
+int sfp_tie_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const uint64_t* s0,
+                   const uint64_t* s1, const uint64_t* w, const uint64_t* k, sfp_limbs m) {
+    // the constants ride in the kernel's argument block (no upload, no ring
+    // slot: capturable, any lane); 16-byte accesses need aligned rows
+    if (!m.count || m.count > SFP_MAX_LIMBS || d->n < 2) return -1;
+    if ((((uintptr_t)d0 | (uintptr_t)d1 | (uintptr_t)d2 | (uintptr_t)s0 | (uintptr_t)s1 | (uintptr_t)w) & 15) != 0)
+        return -1;
+    if (!limbsOk(d, m, "tie_tensor")) return -1;
+    ConstArgs ka;
+    std::memcpy(ka.k, k, m.count * 8);
+    std::memset(ka.k + m.count, 0, (SFP_MAX_LIMBS - m.count) * 8);
+    const size_t total = (size_t)m.count * d->n;
+    SFP_GO(k_tie_tensor, dim3(ewGrid(total / 2)), dim3(kThreads), d0, d1, d2, s0, s1, w, ka, m, d->bar, d->logn);
+    checkLaunch(d, "tie_tensor");
+    return 0;
 }
 
 void sfp_lin_wsum(sfp_dev* d, uint64_t* out, const uint64_t* const* ins, const uint64_t* k,

@@ -333,6 +333,21 @@ SFP_OPTIONAL int sfp_moddown_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* o
 SFP_OPTIONAL int sfp_rescale_add(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, const uint64_t* qlinv,
                                  uint32_t npoly, size_t in_stride, size_t out_stride, const uint64_t* cst);
 
+// ---- optional: the tie-aware rank term's tensor (stable rank sort) ---------------
+// With (u0, u1) = (w s0 + k, w s1) -- s a ciphertext (s0, s1), w a plaintext,
+// k[limb] host residues, all m.count rows in the evaluation domain -- the
+// tensor of s and u in ONE launch:
+//   d0 = s0 u0,  d1 = s0 u1 + s1 u0,  d2 = s1 u1
+// u is never stored.  The canonical residues of sfp_mul (u0 = s0 w, u1 = s1 w),
+// sfp_add_const (u0 += k) and sfp_tensor(s, u): four launches.  The outputs
+// may not overlap the inputs.  k travels in the kernel's arguments: no upload
+// and no host synchronisation, so the prim may be captured and issued on any
+// lane.  Weak like the prims above: where its address is null (the C oracle),
+// or it returns -1 (a shape it does not handle: nothing done), the host layer
+// runs the four prims.
+SFP_OPTIONAL int sfp_tie_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const uint64_t* s0,
+                                const uint64_t* s1, const uint64_t* w, const uint64_t* k, sfp_limbs m);
+
 // ---- optional: CKKS decoding on the device (the end of a decryption) ----------
 // `count` row sets src + b * srcStride, each nl (1 or 2) COEFFICIENT-domain
 // rows of n words modulo primes 0 .. nl-1 (c0 + c1 s after its inverse NTT),

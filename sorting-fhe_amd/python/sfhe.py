@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "sfhe_encode_counts", "sfhe_bootstrap_graphs",
     "sfhe_decrypt_batch", "sfhe_decode_counts",
     "sfhe_encrypt_batch", "sfhe_sample_counts",
+    "sfhe_sorter_sort_stable", "sfhe_sorter_rank_stable", "sfhe_tie_counts",
 ]
 
 
@@ -171,6 +172,9 @@ _SIGS = {
     "sfhe_decode_counts": (C.c_int, [_VP, _PU64, _PU64]),
     "sfhe_encrypt_batch": (C.c_int, [_VP, _PD, _SZ, _PSZ, _SZ, _U32, _PU32, C.POINTER(_VP)]),
     "sfhe_sample_counts": (C.c_int, [_VP, _PU64, _PU64]),
+    "sfhe_sorter_sort_stable": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _PVP]),
+    "sfhe_sorter_rank_stable": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _PVP]),
+    "sfhe_tie_counts": (C.c_int, [_VP, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -479,6 +483,12 @@ class Engine:
         self._chk(self.lib.sfhe_decode_counts(self.ctx, C.byref(d), C.byref(h)))
         return d.value, h.value
 
+    def tie_counts(self):
+        """(fused, composed) tie-term tensors of the stable rank since the last op_stats reset."""
+        f, c = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_tie_counts(self.ctx, C.byref(f), C.byref(c)))
+        return f.value, c.value
+
     # -- eval --
     def add(self, a, b):
         return self._new(self.lib.sfhe_eval_add, self.ctx, a.h, b.h)
@@ -617,6 +627,15 @@ class Sorter:
 
     def rank(self, ct: Ct, n: int = 3, dg: int = 2, df: int = 2) -> Ct:
         return self.eng._new(self.eng.lib.sfhe_sorter_rank, self.h, ct.h, n, dg, df)
+
+    def sort_stable(self, ct: Ct, n: int = 3, dg: int = 2, df: int = 2) -> Ct:
+        """Tie-aware sort: duplicate values sort, equal values in input order.
+        Needs mult_depth = direct_sort_params' depth + 1 (SfheError otherwise)."""
+        return self.eng._new(self.eng.lib.sfhe_sorter_sort_stable, self.h, ct.h, n, dg, df)
+
+    def rank_stable(self, ct: Ct, n: int = 3, dg: int = 2, df: int = 2) -> Ct:
+        """#{j : x_j < x_r} + #{j < r : x_j = x_r}; one level below rank()'s."""
+        return self.eng._new(self.eng.lib.sfhe_sorter_rank_stable, self.h, ct.h, n, dg, df)
 
     def place(self, rank: Ct, ct: Ct) -> Ct:
         return self.eng._new(self.eng.lib.sfhe_sorter_place, self.h, rank.h, ct.h)
