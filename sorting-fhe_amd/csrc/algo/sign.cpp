@@ -8,7 +8,9 @@
 // coefficient multiplications happen at depth 1.
 #include "sign.h"
 
+#include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <map>
 #include <vector>
 
@@ -17,6 +19,16 @@ using namespace lbcrypto;
 namespace {
 
 using Ct = Ciphertext<DCRTPoly>;
+
+// c x at level `at` (> x's level)
+Ct constTermAt(const CryptoContext<DCRTPoly>& cc, const Ct& x, double c, uint32_t at) {
+    const uint64_t *r0, *r1;
+    std::vector<DeviceBufferPtr> keep;
+    cc->RowsAt(x, at - 1, &r0, &r1, keep);  // settled (and gathered into a replicated tail)
+    const std::vector<const uint64_t*> i0{r0}, i1{r1};
+    const std::vector<double> w{c}, sc{x->scale};
+    return cc->LinearWSumRescale(i0, i1, w, at - 1, x->GetSlots(), &sc);
+}
 
 // sum_{i} c[i] x^(2i+1) for c.size() == 2^(k-1) odd coefficients, depth k:
 //   P(x) = A(x) + B(x) * x^(2^(k-1)),  A,B of half the degree.
@@ -36,15 +48,7 @@ struct OddPoly {
     const std::vector<Ct>& pw;
     std::map<std::pair<size_t, uint32_t>, Ct> aligned;
 
-    // c x at level `at` (> x's level)
-    Ct constAt(double c, uint32_t at) {
-        const uint64_t *r0, *r1;
-        std::vector<DeviceBufferPtr> keep;
-        cc->RowsAt(x, at - 1, &r0, &r1, keep);  // settled (and gathered into a replicated tail)
-        const std::vector<const uint64_t*> i0{r0}, i1{r1};
-        const std::vector<double> w{c}, sc{x->scale};
-        return cc->LinearWSumRescale(i0, i1, w, at - 1, x->GetSlots(), &sc);
-    }
+    Ct constAt(double c, uint32_t at) { return constTermAt(cc, x, c, at); }
     const Ct& power(size_t j, uint32_t level) {
         if (pw[j]->GetLevel() >= level) return pw[j];
         auto key = std::make_pair(j, level);
@@ -74,7 +78,117 @@ struct OddPoly {
     }
 };
 
+// SFHE_SIGN_BATCH=0: OddPoly::eval's issue order (every op alone, when its
+// consumer asks for it).  Read once.
+bool signBatch() {
+    static const bool on = [] {
+        const char* v = std::getenv("SFHE_SIGN_BATCH");
+        return !v || *v != '0';
+    }();
+    return on;
+}
+
+// OddPoly's tree -- the same nodes, levels, coefficient terms, aligned powers
+// and sums -- issued wave by wave: the tree is built first (no device work),
+// then every wave's products -- the next power x^(2^j) and the nodes'
+// B(x) * x^(2^j) whose operands exist (degree 7: x^2 | x^4, (c3 x) x^2 |
+// B x^4, (c1 x) x^2) -- go out through MaterializeMany, which batches those
+// of one level, so their identical launches merge.  The coefficient terms
+// (they depend on x alone: all after the first wave) and the alignment of a
+// power (after the wave that made it) follow the wave's products one by one:
+// batching them as well gave wrong rows in larger sorts.
+// A node's sum follows the wave of its product, as before.  Every op sees
+// the operands it saw in OddPoly::eval, in the same form: a product's sum
+// partner `lo` is canonical at the product's own level (`want` lands it
+// there), so the sum takes the product's canonical form there as well.
+struct OddPolyWaves {
+    const CryptoContext<DCRTPoly>& cc;
+    const Ct& x;
+    const uint32_t L;  // x's level; x^(2^(j+1)) is at L + j + 1
+    struct Node {
+        const double* c;
+        size_t cnt, j;
+        uint32_t Lp;  // a leaf's level / the level of the node's product and sum
+        int hi, lo;
+        Ct prod, out;
+    };
+    std::vector<Node> nodes;
+    std::vector<Ct> pw;
+    std::map<std::pair<size_t, uint32_t>, Ct> aligned;
+
+    uint32_t pwLevel(size_t j) const { return L + 1 + (uint32_t)j; }
+    uint32_t natural(size_t cnt) const {
+        if (cnt == 1) return L + 1;
+        const size_t half = cnt / 2;
+        return std::max(natural(half), pwLevel(OddPoly::powIndex(half))) + 1;
+    }
+    // OddPoly::eval(c, cnt, want) as a node (children first)
+    int build(const double* c, size_t cnt, uint32_t want) {
+        Node nd{c, cnt, 0, 0, -1, -1, nullptr, nullptr};
+        if (cnt == 1) {
+            nd.Lp = std::max(L + 1, want);
+        } else {
+            const size_t half = cnt / 2;
+            nd.j = OddPoly::powIndex(half);
+            nd.Lp = std::max(std::max(natural(half), pwLevel(nd.j)) + 1, want);
+            nd.hi = build(c + half, half, nd.Lp - 1);
+            nd.lo = build(c, half, nd.Lp);
+        }
+        nodes.push_back(nd);
+        return (int)nodes.size() - 1;
+    }
+    Ct run(const std::vector<double>& c) {
+        const int root = build(c.data(), c.size(), 0);
+        size_t npw = 1;  // even powers x^2, x^4, ... up to x^(cnt)
+        for (size_t p = 4; p < 2 * c.size(); p *= 2) ++npw;
+        cc->Settle(x);
+        while (!nodes[root].out) {
+            std::vector<Ct> prods;
+            const size_t ready = pw.size();  // the powers earlier waves made
+            if (pw.size() < npw) {
+                pw.push_back(cc->EvalSquare(pw.empty() ? x : pw.back()));
+                prods.push_back(pw.back());
+            }
+            // the node products whose operands exist; a power made by an
+            // earlier wave that a node wants at a higher level is aligned after
+            // this wave's products (once per level), for the next wave
+            std::vector<std::pair<size_t, uint32_t>> align;
+            for (Node& nd : nodes) {
+                if (nd.cnt == 1 || nd.prod || nd.j >= ready) continue;
+                const Ct* power = &pw[nd.j];
+                if (pwLevel(nd.j) < nd.Lp - 1) {
+                    const auto key = std::make_pair(nd.j, nd.Lp - 1);
+                    auto it = aligned.find(key);
+                    if (it == aligned.end()) {
+                        if (std::find(align.begin(), align.end(), key) == align.end()) align.push_back(key);
+                        continue;
+                    }
+                    power = &it->second;
+                }
+                if (!nodes[nd.hi].out) continue;
+                nd.prod = cc->EvalMult(nodes[nd.hi].out, *power);
+                prods.push_back(nd.prod);
+            }
+            const bool first = ready == 0;
+            if (prods.empty() && align.empty() && !first)
+                throw OpenFHEException("internal: odd-polynomial wave evaluation stalled");
+            cc->MaterializeMany(prods, std::vector<char>(prods.size(), 0));
+            if (first)  // the coefficient terms need x alone (held until their sums: a few rows longer than before)
+                for (Node& nd : nodes)
+                    if (nd.cnt == 1) nd.out = constTermAt(cc, x, nd.c[0], nd.Lp);
+            for (const auto& key : align) aligned[key] = cc->AdjustLevel(pw[key.first], key.second);
+            for (Node& nd : nodes)
+                if (nd.cnt > 1 && !nd.out && nd.prod && nodes[nd.lo].out) nd.out = cc->EvalAdd(nodes[nd.lo].out, nd.prod);
+        }
+        return nodes[root].out;
+    }
+};
+
 Ct oddPolyFull(const CryptoContext<DCRTPoly>& cc, const Ct& x, const std::vector<double>& c) {
+    if (signBatch() && c.size() > 1) {
+        OddPolyWaves w{cc, x, x->GetLevel(), {}, {}, {}};
+        return w.run(c);
+    }
     // even powers x^2, x^4, ... up to x^(cnt)
     std::vector<Ct> pw;
     pw.push_back(cc->EvalSquare(x));

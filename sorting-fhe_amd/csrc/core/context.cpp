@@ -9,6 +9,8 @@
 // rescaling, which costs no depth on the result (OpenFHE does the same).
 //
 // All polynomial work is enqueued through csrc/prims.h.
+#include <typeindex>
+#include <tuple>
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -1778,6 +1780,7 @@ struct DeferredConstMult : DeferredOp {
     uint32_t level, slots;
     double scale;
     std::vector<uint64_t> k;
+    void sync(SfheContextState* s) override { s->dep(pin.get()); }
     void run(CCI* cc, CtI& ct, bool pending) override {
         SfheContextState* s = cc->state();
         s->dep(pin.get());
@@ -1807,6 +1810,7 @@ struct DeferredPlainMult : DeferredOp {
     uint32_t level, slots;
     double scale;
     Plaintext pt;
+    void sync(SfheContextState* s) override { s->dep(pin.get()); }
     void run(CCI* cc, CtI& ct, bool pending) override {
         SfheContextState* s = cc->state();
         s->dep(pin.get());
@@ -1830,6 +1834,9 @@ struct DeferredMacPlain : DeferredOp {
     std::vector<const uint64_t*> x0, x1;
     std::vector<Plaintext> pts;
     uint32_t level, slots;
+    void sync(SfheContextState* s) override {
+        for (auto& b : pins) s->dep(b.get());
+    }
     void run(CCI* cc, CtI& ct, bool pending) override {
         SfheContextState* s = cc->state();
         for (auto& b : pins) s->dep(b.get());
@@ -1935,6 +1942,10 @@ struct DeferredRelin : DeferredOp {
     DeviceBufferPtr pa, pb;  // the aligned operands' rows, pinned
     const uint64_t *a0, *a1, *b0, *b1;
     uint32_t level, slots;
+    void sync(SfheContextState* s) override {
+        s->dep(pa.get());
+        s->dep(pb.get());
+    }
     void run(CCI* cc, CtI& ct, bool pending) override {
         SfheContextState* s = cc->state();
         s->dep(pa.get());
@@ -2304,6 +2315,59 @@ void CryptoContextImpl<DCRTPoly>::EndBatch() {
     for (auto& e : s->batchFree) s->poolReturn(e.words, e.ptr, e.lane, e.region, s->myLane());
     s->batchFree.clear();
     s->opMu.unlock();  // (BeginBatch's)
+}
+
+void CryptoContextImpl<DCRTPoly>::MaterializeMany(const std::vector<Ciphertext<DCRTPoly>>& cts,
+                                                  const std::vector<char>& pendingOk) {
+    if (cts.size() != pendingOk.size()) SFHE_THROW("MaterializeMany: flag count mismatch");
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    // what is left to run: a deferred op, or pending rows wanted canonical
+    // (a ciphertext already in its consumer's form is left as it is, as
+    // materialize leaves it)
+    struct Item {
+        uint32_t level;        // the level the op works at
+        std::type_index kind;  // the deferred op's type (void: only a rescale of pending rows is left)
+        bool pending;
+        size_t ct;
+        bool like(const Item& o) const { return level == o.level && kind == o.kind && pending == o.pending; }
+    };
+    std::vector<Item> items;
+    for (size_t i = 0; i < cts.size(); ++i) {
+        const auto& c = cts[i];
+        if (!c || (!c->def && !(c->pend && !pendingOk[i]))) continue;
+        const DeferredOp* d = c->def.get();
+        items.push_back({c->level ? c->level - 1 : 0, d ? std::type_index(typeid(*d)) : std::type_index(typeid(void)),
+                         pendingOk[i] != 0, i});
+    }
+    // A batch holds ops of one level, one kind and one form only: lanes that
+    // issue the same launch sequence over the same row counts, which is what
+    // the merged launches are proven on (EvalMultMany, EvalRotateSum).  Lanes
+    // of different levels or kinds gave wrong rows in larger sorts (DESIGN.md
+    // 4b).  A lone rescale of pending rows is never batched.
+    std::stable_sort(items.begin(), items.end(), [](const Item& a, const Item& b) {
+        return std::tie(a.level, a.kind, a.pending) < std::tie(b.level, b.kind, b.pending);
+    });
+    const size_t w = batchWidth();
+    for (size_t b0 = 0, b1; b0 < items.size(); b0 = b1) {
+        const bool lone = items[b0].kind == std::type_index(typeid(void));
+        for (b1 = b0 + 1; !lone && b1 < items.size() && b1 - b0 < w && items[b1].like(items[b0]);) ++b1;
+        // a sharded level's ops exchange rows between the ranks: never batched
+        const bool shard = s->shardAt(s->ellOf(items[b0].level));
+        // waits for other lanes are recorded here, ahead of the batch
+        for (size_t k = b0; k < b1; ++k) {
+            auto& c = *cts[items[k].ct];
+            if (c.def)
+                c.def->sync(s);
+            else
+                s->dep(c.buf.get());
+        }
+        BatchScope bs(this, shard ? 0u : (uint32_t)(b1 - b0));
+        for (size_t k = b0; k < b1; ++k) {
+            bs.lane((uint32_t)(k - b0));
+            SfheInternal::materialize(*cts[items[k].ct], items[k].pending);
+        }
+    }
 }
 
 void CryptoContextImpl<DCRTPoly>::SetPlaintextCache(bool on) {

@@ -620,6 +620,18 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     void BatchLane(uint32_t i);
     void EndBatch();
     uint32_t BatchWidth() const;  // ops per batch (SFHE_BATCH_WIDTH)
+    // Engine extension: run the deferred ops of several independent
+    // ciphertexts as batched ops, one virtual lane each -- cts[i] in the form
+    // its consumer will take: pending rows where pendingOk[i], canonical
+    // otherwise (exactly what the consumer's own materialisation would run:
+    // the same values).  A batch is a run of up to BatchWidth() ops of one
+    // level, one kind (products, plaintext products, ...) and one form;
+    // whatever is alone of its kind, and a rescale of rows already pending,
+    // runs unbatched.  Only batches of canonical ciphertext products are
+    // exercised so far (the sign's waves).  Where batching is unavailable (SFHE_BATCH=0, a sharded level,
+    // an open batch or stacked region, a backend that never merges) the ops
+    // run one after the other.
+    void MaterializeMany(const std::vector<Ciphertext<DCRTPoly>>& cts, const std::vector<char>& pendingOk);
     void SetLane(int lane);
     void JoinLanes();
     // Plaintext-encoding cache across calls (default on); see DESIGN.md.

@@ -43,6 +43,10 @@ struct BootstrapPrecomp;  // bootstrap.cpp
 struct DeferredOp {
     virtual ~DeferredOp() = default;
     virtual void run(CryptoContextImpl<DCRTPoly>* cc, CiphertextImpl<DCRTPoly>& ct, bool pending) = 0;
+    // order the current lane after the writers of the rows run() reads (as
+    // run() does itself; MaterializeMany does it ahead of its batch, where a
+    // wait for another lane cannot be recorded)
+    virtual void sync(SfheContextState* s) = 0;
 };
 
 struct PtCacheEntry {
