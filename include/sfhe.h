@@ -29,7 +29,7 @@ extern "C" {
 /* (sfhe_decrypt_batch and sfhe_decode_counts were added at version 3: additions
  * only, no existing declaration changed, so the version stays; likewise
  * sfhe_encrypt_batch and sfhe_sample_counts, and sfhe_sorter_sort_stable,
- * sfhe_sorter_rank_stable and sfhe_tie_counts) */
+ * sfhe_sorter_rank_stable and sfhe_tie_counts, and sfhe_const_term_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -110,6 +110,12 @@ int sfhe_decode_counts(sfhe_ctx* c, uint64_t* device, uint64_t* host);
  * generic prims since the last sfhe_op_stats reset (SFHE_TIE_FUSED=0, read
  * per call, composes; the results are bit-identical). */
 int sfhe_tie_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
+/* Constant terms c*x at a level (one-input weighted sums: the sign
+ * polynomials' coefficient terms) since the last sfhe_op_stats reset: issued
+ * inside a multi-term launch (sfp_const_terms_rescale), as one fused constant
+ * rescale, and as a weighted sum followed by a rescale (SFHE_CONST_TERMS=0,
+ * read per call, composes; the results are bit-identical). */
+int sfhe_const_term_counts(sfhe_ctx* c, uint64_t* merged, uint64_t* single, uint64_t* composed);
 /* Small polynomials (an encryption's v, e0, e1; the keys' errors and secret)
  * sampled on the device (sfp_sample_small) and on the host since the last
  * sfhe_op_stats reset (SFHE_DEV_SAMPLE=0, read per call, samples on the host;

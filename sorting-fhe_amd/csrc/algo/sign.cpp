@@ -94,9 +94,10 @@ bool signBatch() {
 // B(x) * x^(2^j) whose operands exist (degree 7: x^2 | x^4, (c3 x) x^2 |
 // B x^4, (c1 x) x^2) -- go out through MaterializeMany, which batches those
 // of one level, so their identical launches merge.  The coefficient terms
-// (they depend on x alone: all after the first wave) and the alignment of a
-// power (after the wave that made it) follow the wave's products one by one:
-// batching them as well gave wrong rows in larger sorts.
+// (they depend on x alone: all after the first wave, as one multi-term
+// constant rescale, ConstTermsRescale) and the alignment of a power (after the
+// wave that made it) follow the wave's products outside any batch: batching
+// them as well gave wrong rows in larger sorts.
 // A node's sum follows the wave of its product, as before.  Every op sees
 // the operands it saw in OddPoly::eval, in the same form: a product's sum
 // partner `lo` is canonical at the product's own level (`want` lands it
@@ -173,9 +174,19 @@ struct OddPolyWaves {
             if (prods.empty() && align.empty() && !first)
                 throw OpenFHEException("internal: odd-polynomial wave evaluation stalled");
             cc->MaterializeMany(prods, std::vector<char>(prods.size(), 0));
-            if (first)  // the coefficient terms need x alone (held until their sums: a few rows longer than before)
+            if (first) {
+                // the coefficient terms need x alone (held until their sums: a
+                // few rows longer than before): constant rescales of one input,
+                // up to four in one launch pair per direction (ConstTermsRescale;
+                // no batch is involved)
+                std::vector<std::pair<double, uint32_t>> terms;
+                for (const Node& nd : nodes)
+                    if (nd.cnt == 1) terms.emplace_back(nd.c[0], nd.Lp);
+                const auto cts = cc->ConstTermsRescale(x, terms);
+                size_t t = 0;
                 for (Node& nd : nodes)
-                    if (nd.cnt == 1) nd.out = constTermAt(cc, x, nd.c[0], nd.Lp);
+                    if (nd.cnt == 1) nd.out = cts[t++];
+            }
             for (const auto& key : align) aligned[key] = cc->AdjustLevel(pw[key.first], key.second);
             for (Node& nd : nodes)
                 if (nd.cnt > 1 && !nd.out && nd.prod && nodes[nd.lo].out) nd.out = cc->EvalAdd(nodes[nd.lo].out, nd.prod);

@@ -375,6 +375,15 @@ int sfhe_tie_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
     return SFHE_OK;
 }
 
+int sfhe_const_term_counts(sfhe_ctx* c, uint64_t* merged, uint64_t* single, uint64_t* composed) {
+    REQUIRE(c && merged && single && composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *merged = s.const_merged;
+    *single = s.const_single;
+    *composed = s.const_composed;
+    return SFHE_OK;
+}
+
 void sfhe_ct_free(sfhe_ct* ct) { delete ct; }
 
 int sfhe_ct_clone(const sfhe_ct* ct, sfhe_ct** out) {

@@ -3967,6 +3967,44 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::LinearWSumRescale(
     const uint32_t ell = s->ellOf(level);
     if (ell < 2) SFHE_THROW("no levels left (multiplicative depth exhausted)");
     if (inScale && inScale->size() != w.size()) SFHE_THROW("LinearWSumRescale: scale count");
+    if (w.size() == 1) {
+        // one input: Rescale(k x) is the fused constant rescale (the multiply
+        // on the dropped row's load and on `ein` of the last pass), the same
+        // integers without the weighted-sum launch and its temporary
+        if (constTerms() && SfheInternal::fusedRescale() && !s->shardAt(ell) && in1[0] >= in0[0]) {
+            std::vector<uint64_t> kk;
+            weightResidues(s, w[0], level, ell, kk, inScale ? (*inScale)[0] : 0.0);
+            auto out = SfheInternal::newCt(this, level + 1, slots);
+            const size_t inStride = (size_t)(in1[0] - in0[0]), outStride = (size_t)(out->c1 - out->c0);
+            std::vector<uint64_t> cst;
+            if (constant != 0.0 && psFma() && sfp_mul_const_rescale_add) {
+                cst = SfheInternal::constResidues(s, constant * s->scale[level + 1], ell - 1);
+                cst.resize(2 * cst.size(), 0);
+            }
+            const bool cstDone =
+                !cst.empty() && sfp_mul_const_rescale_add(s->dev, out->c0, in0[0], kk.data(), ell,
+                                                          s->qInvTable[ell].data(), 2, inStride, outStride,
+                                                          cst.data()) == 0;
+            if (!cstDone)
+                sfp_mul_const_rescale(s->dev, out->c0, in0[0], kk.data(), ell, s->qInvTable[ell].data(), 2, inStride,
+                                      outStride);
+            if (psFma() && sfp_mul_const_rescale_add) s->pairedWsums++;  // (both polynomials in each launch)
+            s->stats.const_single++;
+            s->stats.constmult++;
+            s->stats.rescale++;
+            s->countBytes(4.0 * ell * s->n * 8);
+            out = SfheInternal::traced(this, out, "LinearWSumRescale");
+            if (cstDone) {
+                s->fusedConsts++;
+                s->stats.add++;
+                s->countBytes(4.0 * (ell - 1) * s->n * 8);
+            } else if (constant != 0.0) {
+                out = EvalAdd(out, constant);
+            }
+            return out;
+        }
+        s->stats.const_composed++;
+    }
     // c0 and c1 take the same kernel over different rows: one merged launch
     // (two virtual lanes of a batch), where no batch is open already
     BatchScope pairLanes(this, psFma() && !s->shardAt(ell) ? 2u : 0u);
@@ -4021,6 +4059,56 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::LinearWSumRescale(
         s->countBytes(4.0 * (ell - 1) * s->n * 8);
     } else if (constant != 0.0) {
         out = EvalAdd(out, constant);
+    }
+    return out;
+}
+
+std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::ConstTermsRescale(
+    const Ciphertext<DCRTPoly>& x, const std::vector<std::pair<double, uint32_t>>& terms) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    SfheInternal::deps(s, {&x});  // settled once, for every term
+    std::vector<Ciphertext<DCRTPoly>> out(terms.size());
+    for (const auto& t : terms) {
+        if (t.second > s->L) SFHE_THROW("no levels left (multiplicative depth exhausted)");
+        if (t.second <= x->level) SFHE_THROW("ConstTermsRescale: a term's level is not above the input's");
+    }
+    // x's rows all local: so are the rows of every limb count below its own
+    const bool merge = constTerms() && SfheInternal::fusedRescale() && sfp_const_terms_rescale &&
+                       !s->shardAt(s->ellOf(x->level)) && x->c1 >= x->c0;
+    for (size_t done = 0; done < terms.size();) {
+        const size_t take = merge ? std::min<size_t>(SFP_MAX_CONST_TERMS, terms.size() - done) : 1;
+        if (take < 2) {  // one by one: LinearWSumRescale's one-input route
+            const uint32_t level = terms[done].second - 1;
+            const uint64_t *r0, *r1;
+            std::vector<DeviceBufferPtr> keep;
+            RowsAt(x, level, &r0, &r1, keep);
+            const std::vector<const uint64_t*> i0{r0}, i1{r1};
+            const std::vector<double> w{terms[done].first}, sc{x->scale};
+            out[done] = LinearWSumRescale(i0, i1, w, level, x->slots, &sc);
+            ++done;
+            continue;
+        }
+        std::vector<uint64_t> kk[SFP_MAX_CONST_TERMS];
+        sfp_const_term ts[SFP_MAX_CONST_TERMS];
+        for (size_t j = 0; j < take; ++j) {
+            const uint32_t level = terms[done + j].second - 1, ell = s->ellOf(level);
+            weightResidues(s, terms[done + j].first, level, ell, kk[j], x->scale);
+            auto ct = SfheInternal::newCt(this, level + 1, x->slots);
+            ts[j] = sfp_const_term{ell, kk[j].data(), s->qInvTable[ell].data(), ct->c0, (size_t)(ct->c1 - ct->c0),
+                                   nullptr};
+            out[done + j] = ct;
+            s->stats.constmult++;
+            s->stats.rescale++;
+            s->countBytes(4.0 * ell * s->n * 8);
+        }
+        // 1: one launch pair per direction; 0: the prim issued them one by one;
+        // < 0: nothing issued (the device error surfaces at the next check)
+        const int how = sfp_const_terms_rescale(s->dev, x->c0, (size_t)(x->c1 - x->c0), 2, ts, (uint32_t)take);
+        if (how >= 0) (how == 1 ? s->stats.const_merged : s->stats.const_single) += take;
+        if (psFma()) s->pairedWsums += take;  // (both polynomials in each launch)
+        for (size_t j = 0; j < take; ++j) out[done + j] = SfheInternal::traced(this, out[done + j], "LinearWSumRescale");
+        done += take;
     }
     return out;
 }

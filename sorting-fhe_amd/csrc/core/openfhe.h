@@ -538,6 +538,18 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
                                            const std::vector<const uint64_t*>& in1,
                                            const std::vector<double>& w, uint32_t level,
                                            uint32_t slots, const std::vector<double>* inScale, double constant);
+    // A call with one input at a level whose rows are not dealt over ranks is
+    // a constant rescale: sfp_mul_const_rescale(_add), no weighted-sum launch
+    // and no temporary (SFHE_CONST_TERMS=0, read per call: as a sum, then a
+    // rescale; the same integers).
+    // Engine extension: terms[j] = (c_j, at_j): c_j * x at level at_j (> x's
+    // level), each what LinearWSumRescale({x}, {c_j}, at_j - 1) gives.  Up to
+    // SFP_MAX_CONST_TERMS of them share one inverse and one forward NTT launch
+    // pair (sfp_const_terms_rescale) where the backend has that prim and x's
+    // rows are not dealt over ranks; else (the C oracle, SFHE_CONST_TERMS=0)
+    // they are formed one by one.
+    std::vector<Ciphertext<DCRTPoly>> ConstTermsRescale(const Ciphertext<DCRTPoly>& x,
+                                                        const std::vector<std::pair<double, uint32_t>>& terms);
     // Engine extension: nout weighted sums of the same inputs in one pass
     // (one multi-output kernel + one batched rescale); w[o] has nin weights.
     std::vector<Ciphertext<DCRTPoly>> LinearWSumRescaleMulti(
@@ -646,6 +658,9 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         double algo_bytes = 0.0;  // SURVEY.md §8(d) byte model
         uint64_t pool_bytes = 0;  // device memory held by the context's pool (live + free blocks)
         uint64_t tie_fused = 0, tie_composed = 0;  // EvalTieTerm tensors in one launch / composed of generic prims
+        // constant terms c x (one-input weighted sums): inside a multi-term launch
+        // (sfp_const_terms_rescale) / as one fused constant rescale / as a weighted sum, then a rescale
+        uint64_t const_merged = 0, const_single = 0, const_composed = 0;
     };
     OpStats GetOpStats() const;
     void ResetOpStats();

@@ -201,7 +201,9 @@ struct SfheContextState {
     uint32_t lazyHold = 0;
     // sums the backend folded into the producing op's last pass (prims.h
     // sfp_*_add): ciphertext addends, constants, and weighted sums whose two
-    // polynomials went out as one launch (reported under SFHE_PS_DEBUG)
+    // polynomials went out as one launch (reported under SFHE_PS_DEBUG; a
+    // one-input sum taken as a fused constant rescale on a backend with the
+    // sum-folding prims is one launch for both polynomials as well)
     uint64_t fusedSums = 0, fusedConsts = 0, pairedWsums = 0;
     std::set<uint64_t> abandonedEpochs;        // captures that were abandoned (their work never ran)
     std::vector<std::pair<uint64_t*, size_t>> capAllocs;
@@ -318,6 +320,15 @@ inline bool psFma() {
         return !v || *v != '0';
     }();
     return on;
+}
+
+// SFHE_CONST_TERMS=0 (read per call): a one-input weighted sum runs the
+// weighted-sum kernel and a separate rescale instead of the fused constant
+// rescale, and the sign's coefficient terms go out one by one (A/B knob; the
+// same values)
+inline bool constTerms() {
+    const char* v = std::getenv("SFHE_CONST_TERMS");
+    return !v || *v != '0';
 }
 
 // Serialises host-side use of a context and routes the calling thread's

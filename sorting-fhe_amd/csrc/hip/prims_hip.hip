@@ -5550,19 +5550,16 @@ void sfp_rescale(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, co
 // Rescale of in * w: w = mulRows (elementwise, ell rows shared by the polys),
 // w = mulK (host array of ell per-row residues) or w = 1.  The dropped row is
 // multiplied on its INTT's load, the kept rows in the epilogue.
-static void rescaleCore(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, uint32_t dropPrime,
-                        const uint64_t* qlinv, uint32_t npoly, size_t inStride, size_t outStride,
-                        const uint64_t* mulRows, const uint64_t* mulK, const uint64_t* cst = nullptr) {
+// The two row groups of one such rescale: A the dropped rows' INTT (into
+// `last`, npoly rows), B the lift + forward NTT of the kept rows with the
+// subtract-multiply epilogue (intermediate in `tmp`, npoly * (ell - 1) rows).
+static void rescaleGroups(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, uint32_t dropPrime,
+                          const uint64_t* qlinv, uint32_t npoly, size_t inStride, size_t outStride,
+                          const uint64_t* mulRows, const uint64_t* mulK, const uint64_t* cst, u64* last, u64* tmp,
+                          RowGroup& A, RowGroup& B) {
     const uint32_t n = d->n;
     const uint32_t cnt = ell - 1;
-    if (cnt > SFP_MAX_LIMBS || ell < 2) {
-        record(d, "rescale (limb count)", hipErrorInvalidValue);
-        return;
-    }
-    u64* last = scratch(d, (size_t)npoly * n + (size_t)npoly * cnt * n);
-    if (!last) return;
-    u64* tmp = last + (size_t)npoly * n;
-    RowGroup A = rowsOf(npoly, 1, sfp_limbs{1, 0, dropPrime, 0});
+    A = rowsOf(npoly, 1, sfp_limbs{1, 0, dropPrime, 0});
     A.src = RowPtr{in + (size_t)cnt * n, (long long)inStride, 0};
     A.dst = RowPtr{last, (long long)n, 0};
     // per-call multipliers: content-cached device constants (a miss uploads
@@ -5583,8 +5580,7 @@ static void rescaleCore(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t 
         A.preK = dmk + 2 * cnt;
         A.preKS = dmk + 2 * cnt + 1;
     }
-    nttRows(d, A, 1);
-    RowGroup B = rowsOf(npoly, cnt, sfp_limbs{cnt, cnt, 0, 0});
+    B = rowsOf(npoly, cnt, sfp_limbs{cnt, cnt, 0, 0});
     B.src = RowPtr{last, (long long)n, 0};
     B.lift = 1;
     B.liftPrime = dropPrime;
@@ -5608,6 +5604,23 @@ static void rescaleCore(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t 
         B.emKS = dmk + cnt;
     }
     if (cst) B.ecst = devConst(d, cst, (size_t)npoly * cnt);  // (+ per-row constants: sfp_rescale_add)
+}
+
+static void rescaleCore(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, uint32_t dropPrime,
+                        const uint64_t* qlinv, uint32_t npoly, size_t inStride, size_t outStride,
+                        const uint64_t* mulRows, const uint64_t* mulK, const uint64_t* cst = nullptr) {
+    const uint32_t n = d->n;
+    const uint32_t cnt = ell - 1;
+    if (cnt > SFP_MAX_LIMBS || ell < 2) {
+        record(d, "rescale (limb count)", hipErrorInvalidValue);
+        return;
+    }
+    u64* last = scratch(d, (size_t)npoly * n + (size_t)npoly * cnt * n);
+    if (!last) return;
+    RowGroup A, B;
+    rescaleGroups(d, out, in, ell, dropPrime, qlinv, npoly, inStride, outStride, mulRows, mulK, cst, last,
+                  last + (size_t)npoly * n, A, B);
+    nttRows(d, A, 1);
     nttRows(d, B, 0);
 }
 
@@ -5630,6 +5643,134 @@ void sfp_mul_const_rescale(sfp_dev* d, uint64_t* out, const uint64_t* in, const 
 void sfp_mul_rescale(sfp_dev* d, uint64_t* out, const uint64_t* in, const uint64_t* m, uint32_t ell,
                      const uint64_t* qlinv, uint32_t npoly, size_t inStride, size_t outStride) {
     rescaleCore(d, out, in, ell, ell - 1, qlinv, npoly, inStride, outStride, m, nullptr);
+}
+
+int sfp_mul_const_rescale_add(sfp_dev* d, uint64_t* out, const uint64_t* in, const uint64_t* k, uint32_t ell,
+                              const uint64_t* qlinv, uint32_t npoly, size_t inStride, size_t outStride,
+                              const uint64_t* cst) {
+    rescaleCore(d, out, in, ell, ell - 1, qlinv, npoly, inStride, outStride, nullptr, k, cst);
+    return 0;
+}
+
+// The shapes one row-group-set launch pair takes (nttRowsMulti): 2..4 sets
+// on a ring of more than one tile, fewer than 65 536 grid rows and below the
+// LE = 3 row counts (whose kernels have no multi-set form).  Anything else
+// goes to nttRows group by group.
+static bool rowSetsShape(const sfp_dev* d, uint32_t cnt, uint32_t totalRows) {
+    return cnt >= 2 && cnt <= 4 && d->n > (uint32_t)kNttTile && totalRows <= 65535u &&
+           totalRows < (uint32_t)kNttSmallRows;
+}
+
+// Both passes of an NTT over 2 <= cnt <= 4 plain row groups (no fused
+// conversion) as one launch pair: one RowGroupSet launch per pass, a set per
+// group -- alternating rows where the groups fill the sets with equal row
+// counts, else concatenated (launchSets).  Issued directly, each launch on its
+// own (no merge class).  Tile by the launch's total rows, as nttRows picks it
+// for one group.  The caller has checked rowSetsShape; false (an error is
+// recorded, nothing issued) for groups this launcher cannot take.
+static bool nttRowsMulti(sfp_dev* d, const RowGroup* G, int cnt, int inverse) {
+    const RowGroup* ptr[4];
+    uint32_t rows[4], total = 0;
+    bool ok = cnt >= 2 && cnt <= 4;
+    for (int i = 0; ok && i < cnt; ++i) {
+        ptr[i] = &G[i];
+        rows[i] = G[i].P * G[i].R;
+        total += rows[i];
+        ok = rows[i] && !G[i].md && !G[i].cy && G[i].pm.count == G[i].R && limbsOk(d, G[i].pm, "ntt") &&
+             !(G[i].lift && G[i].liftPrime >= d->np);
+    }
+    if (!ok || !rowSetsShape(d, (uint32_t)cnt, total)) {
+        record(d, "ntt (row-group sets: shape)", hipErrorInvalidValue);
+        return false;
+    }
+    const u64* tw = inverse ? d->ipsi : d->psi;
+    const u64* twS = inverse ? d->ipsiS : d->psiS;
+    const double* twD = inverse ? d->ipsiD : d->psiD;
+    const double* rowD = inverse ? d->irowD : d->rowD;
+    const bool t1k = total <= nttT1kRows() && d->n <= (uint32_t)kNttSmallTile * 128u;
+    const double bytes = 16.0 * total * d->n;
+    const int fp = nttFp();
+    auto pass = [&](auto k2, auto k4, uint32_t tile) {
+        timedLaunch(d, SFP_FAM_NTT, bytes, [&] {
+            auto launch = [&](const auto& S, uint32_t tot) {
+                using SetT = std::decay_t<decltype(S)>;
+                constexpr int NG = sizeof(SetT::a) / sizeof(RowGroup);
+                NttKernN<NG> k;
+                if constexpr (NG == 2)
+                    k = k2;
+                else
+                    k = k4;
+                const dim3 g(d->n / tile, tot);
+                const int threads = (int)(tile >> 2);
+                StackRec r;
+                r.go = [=](hipStream_t s_) {
+                    hipLaunchKernelGGL(k, g, dim3(threads), 0, s_, S, d->bar, tw, twS, d->ninv, d->ninvS, d->logn, twD,
+                                       d->qinvD, d->ninvD, d->ninvQ, fp, rowD);
+                };
+                issueRec(d, std::move(r));
+            };
+            if (cnt == 2)
+                launchSets<RowGroup, 2>(ptr, rows, cnt, launch);
+            else
+                launchSets<RowGroup, 4>(ptr, rows, cnt, launch);
+        });
+    };
+    auto passes = [&](auto tileC) {
+        constexpr int TL = decltype(tileC)::value;
+        if (inverse) {
+            pass(k_ntt<true, false, 2, TL, 2>, k_ntt<true, false, 2, TL, 4>, TL);
+            pass(k_ntt<true, true, 2, TL, 2>, k_ntt<true, true, 2, TL, 4>, TL);
+        } else {
+            pass(k_ntt<false, true, 2, TL, 2>, k_ntt<false, true, 2, TL, 4>, TL);
+            pass(k_ntt<false, false, 2, TL, 2>, k_ntt<false, false, 2, TL, 4>, TL);
+        }
+    };
+    if (t1k)
+        passes(std::integral_constant<int, kNttSmallTile>{});
+    else
+        passes(std::integral_constant<int, kNttTile>{});
+    checkLaunch(d, "ntt (row-group sets)");
+    return true;
+}
+
+// 2 <= m <= SFP_MAX_CONST_TERMS rescales of constant multiples of one input
+// (term j: Rescale(in * k_j) at ell_j limbs, + cst_j) as one inverse launch
+// pair over every term's dropped rows and one forward pair over every term's
+// kept rows; one scratch allocation.  Returns 1 when issued so, 0 when the
+// terms went out one by one (a shape outside rowSetsShape), -1 on an error
+// (recorded; nothing issued).
+int sfp_const_terms_rescale(sfp_dev* d, const uint64_t* in, size_t inStride, uint32_t npoly, const sfp_const_term* t,
+                            uint32_t m) {
+    const uint32_t n = d->n;
+    size_t words = 0;
+    uint32_t inv = 0, fwd = 0;
+    for (uint32_t j = 0; j < m; ++j) {
+        if (t[j].ell < 2 || t[j].ell - 1 > SFP_MAX_LIMBS) {
+            record(d, "const terms rescale (limb count)", hipErrorInvalidValue);
+            return -1;
+        }
+        words += (size_t)npoly * t[j].ell * n;
+        inv += npoly;
+        fwd += npoly * (t[j].ell - 1);
+    }
+    static_assert(SFP_MAX_CONST_TERMS <= 4, "nttRowsMulti takes up to four sets");
+    if (m > SFP_MAX_CONST_TERMS || !rowSetsShape(d, m, inv) || !rowSetsShape(d, m, fwd)) {
+        for (uint32_t j = 0; j < m; ++j)
+            rescaleCore(d, t[j].out, in, t[j].ell, t[j].ell - 1, t[j].qlinv, npoly, inStride, t[j].out_stride, nullptr,
+                        t[j].k, t[j].cst);
+        return 0;
+    }
+    u64* base = scratch(d, words);
+    if (!base) return -1;
+    RowGroup A[SFP_MAX_CONST_TERMS], B[SFP_MAX_CONST_TERMS];
+    for (uint32_t j = 0; j < m; ++j) {
+        rescaleGroups(d, t[j].out, in, t[j].ell, t[j].ell - 1, t[j].qlinv, npoly, inStride, t[j].out_stride, nullptr,
+                      t[j].k, t[j].cst, base, base + (size_t)npoly * n, A[j], B[j]);
+        base += (size_t)npoly * t[j].ell * n;
+    }
+    // (the forward pair reads what the inverse pair wrote: not issued without it)
+    if (!nttRowsMulti(d, A, (int)m, 1) || !nttRowsMulti(d, B, (int)m, 0)) return -1;
+    return 1;
 }
 
 // ---- base conversion / key switching ----

@@ -332,6 +332,34 @@ SFP_OPTIONAL int sfp_moddown_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* o
                                          const uint64_t* r0, const uint64_t* r1, int sign, const uint64_t* cst);
 SFP_OPTIONAL int sfp_rescale_add(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t ell, const uint64_t* qlinv,
                                  uint32_t npoly, size_t in_stride, size_t out_stride, const uint64_t* cst);
+// sfp_mul_const_rescale with sfp_rescale_add's per-row constants: out =
+// Rescale(in * k_i) + cst.
+SFP_OPTIONAL int sfp_mul_const_rescale_add(sfp_dev* d, uint64_t* out, const uint64_t* in, const uint64_t* k,
+                                           uint32_t ell, const uint64_t* qlinv, uint32_t npoly, size_t in_stride,
+                                           size_t out_stride, const uint64_t* cst);
+
+// ---- optional: several constant rescales of one input in one launch pair per direction
+// Term j of m (2 <= m <= SFP_MAX_CONST_TERMS) is sfp_mul_const_rescale(_add)
+// of the input's first ell_j rows: out_j = Rescale(in * k_j) (+ cst_j), k_j
+// ell_j host residues, qlinv_j the ell_j - 1 rescale constants of that limb
+// count, cst_j null or npoly * (ell_j - 1) host residues.  The terms' dropped
+// rows share one inverse NTT launch pair and their kept rows one forward pair
+// (a row-group set per term; terms of different limb counts are sets of
+// different primes and row counts).  The same integers as the m separate
+// calls.  Returns 1 when issued merged, 0 when it issued the terms one by one
+// (one-tile rings, more rows than one launch takes), -1 on an error (recorded,
+// nothing issued).
+#define SFP_MAX_CONST_TERMS 4
+typedef struct {
+    uint32_t ell;
+    const uint64_t* k;
+    const uint64_t* qlinv;
+    uint64_t* out;
+    size_t out_stride;
+    const uint64_t* cst;
+} sfp_const_term;
+SFP_OPTIONAL int sfp_const_terms_rescale(sfp_dev* d, const uint64_t* in, size_t in_stride, uint32_t npoly,
+                                         const sfp_const_term* t, uint32_t m);
 
 // ---- optional: the tie-aware rank term's tensor (stable rank sort) ---------------
 // With (u0, u1) = (w s0 + k, w s1) -- s a ciphertext (s0, s1), w a plaintext,

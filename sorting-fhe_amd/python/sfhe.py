@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "sfhe_decrypt_batch", "sfhe_decode_counts",
     "sfhe_encrypt_batch", "sfhe_sample_counts",
     "sfhe_sorter_sort_stable", "sfhe_sorter_rank_stable", "sfhe_tie_counts",
+    "sfhe_const_term_counts",
 ]
 
 
@@ -175,6 +176,7 @@ _SIGS = {
     "sfhe_sorter_sort_stable": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _PVP]),
     "sfhe_sorter_rank_stable": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _PVP]),
     "sfhe_tie_counts": (C.c_int, [_VP, _PU64, _PU64]),
+    "sfhe_const_term_counts": (C.c_int, [_VP, _PU64, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -488,6 +490,13 @@ class Engine:
         f, c = C.c_uint64(), C.c_uint64()
         self._chk(self.lib.sfhe_tie_counts(self.ctx, C.byref(f), C.byref(c)))
         return f.value, c.value
+
+    def const_term_counts(self):
+        """(merged, single, composed) constant terms c*x since the last op_stats reset: inside a
+        multi-term launch, as one fused constant rescale, as a weighted sum then a rescale."""
+        m, s1, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_const_term_counts(self.ctx, C.byref(m), C.byref(s1), C.byref(c)))
+        return m.value, s1.value, c.value
 
     # -- eval --
     def add(self, a, b):
