@@ -3882,12 +3882,13 @@ __global__ __launch_bounds__(kThreads) void k_fill1(unsigned char* __restrict__ 
 // Inside a stacked region every lane's launches, event records and event
 // waits are recorded per lane instead of issued.  stackFlush then issues them
 // all on streams[0]: each lane's items in that lane's order, a wait only after
-// the record it names, and -- whenever two lanes' next launches are the same
-// kernel over different rows (the sort's two batches run the same op
-// sequence, reference src/sort_algo.h:438-455, 713-742) -- those two as ONE
-// launch whose grid holds the rows of both (ArgSet<T, 2>), or whose job table
-// holds the jobs of both (conversions).  Per-row arithmetic is unchanged, so
-// results are bit-identical; the sort issues about half the launches.
+// the record it names, and -- whenever several lanes' next launches (up to
+// kMergeMax) are the same kernel over different rows (the sort's two batches
+// run the same op sequence, reference src/sort_algo.h:438-455, 713-742; a
+// batched op's lanes likewise) -- those as ONE launch whose grid holds the
+// rows of all (ArgSet<T, NG>, NG = 2, 4 or 8), or whose job table holds the
+// jobs of all (conversions).  Per-row arithmetic is unchanged, so results are
+// bit-identical; the sort's two batches alone issue about half the launches.
 enum { STK_NONE = 0, STK_NTT = 1, STK_KS = 2, STK_CONV = 3, STK_MDRS = 4, STK_Y = 5 };
 
 static uint64_t stkKey(const void* kern, uint32_t a, uint32_t b) {
@@ -3896,34 +3897,115 @@ static uint64_t stkKey(const void* kern, uint32_t a, uint32_t b) {
     return h;
 }
 
-template <int NG>
-using NttKernN = void (*)(RowGroupSet<NG>, const sf_barrett*, const u64*, const u64*, const u64*, const u64*,
-                          uint32_t, const double*, const double*, const double*, const double*, int, const double*);
-using NttKern2 = NttKernN<2>;
-using NttKern4 = NttKernN<4>;
-using NttKern8 = NttKernN<8>;
-struct NttPay {
-    RowGroup G;
-    uint32_t rows;
-    dim3 g;
-    int threads, useFp;
-    NttKern2 k2;
-    NttKern4 k4;
-    NttKern8 k8;
+// A kernel family: one kernel over ArgSet<A, NG> at 1, 2, 4 and 8 argument
+// sets (Tail: its arguments after the set), with its block size.  A null
+// slot: no merged form at that width.  The factories below are the one place
+// a family's instantiations are named -- the launch sites, the merged
+// launches and graph timing's family table (kernelFamily) all read them.
+template <class A, class... Tail>
+struct SetKerns {
+    using Args = A;
+    template <int NG>
+    using K = void (*)(ArgSet<A, NG>, Tail...);
+    K<1> k1;
+    K<2> k2;
+    K<4> k4;
+    K<8> k8;
+    int tile;     // words per block (grid.x = n / tile); 0: the grid.y arg-set kernels
+    int threads;  // per block
+    template <int NG>
+    K<NG> get() const {
+        if constexpr (NG == 1)
+            return k1;
+        else if constexpr (NG == 2)
+            return k2;
+        else if constexpr (NG == 4)
+            return k4;
+        else
+            return k8;
+    }
+    const void* form(int ng) const {
+        return ng == 1 ? (const void*)k1 : ng == 2 ? (const void*)k2 : ng == 4 ? (const void*)k4 : (const void*)k8;
+    }
+    // the sets of the form that f (not null) is; 0: not of this family
+    int widthOf(const void* f) const {
+        for (int ng : {1, 2, 4, 8})
+            if (form(ng) == f) return ng;
+        return 0;
+    }
+};
+// f(NG) with the ArgSet width that holds cnt sets (1, 2, 4 or 8), as a constant
+template <class F>
+static auto withWidth(int cnt, F&& f) {
+    if (cnt == 1) return f(std::integral_constant<int, 1>{});
+    if (cnt == 2) return f(std::integral_constant<int, 2>{});
+    if (cnt <= 4) return f(std::integral_constant<int, 4>{});
+    return f(std::integral_constant<int, 8>{});
+}
+// (Each specialisation is named in an initialiser of its own: named only
+// inside a conditional expression, the device code of some was never emitted
+// -- "Cannot find Symbol" at launch.)
+using NttKerns = SetKerns<RowGroup, const sf_barrett*, const u64*, const u64*, const u64*, const u64*, uint32_t,
+                          const double*, const double*, const double*, const double*, int, const double*>;
+template <bool INV, bool COL, int LE, int TILE, bool CONV = false>
+static NttKerns nttKerns() {
+    if constexpr (LE == 2)
+        return {k_ntt<INV, COL, LE, TILE, 1, CONV>, k_ntt<INV, COL, LE, TILE, 2, CONV>,
+                k_ntt<INV, COL, LE, TILE, 4, CONV>, k_ntt<INV, COL, LE, TILE, 8, CONV>, TILE, TILE >> LE};
+    else  // (kNttSmallRows rows or more: never merged)
+        return {k_ntt<INV, COL, LE, TILE, 1, CONV>, nullptr, nullptr, nullptr, TILE, TILE >> LE};
+}
+template <int TILE, int TG>
+static NttKerns modupColKerns() {
+    return {k_modup_col<TILE, 1, TG>, k_modup_col<TILE, 2, TG>, k_modup_col<TILE, 4, TG>, k_modup_col<TILE, 8, TG>,
+            TILE, TILE >> 2};
+}
+template <int TILE, int TG>
+static NttKerns moddownColKerns() {
+    return {k_moddown_col<TILE, 1, TG>, k_moddown_col<TILE, 2, TG>, k_moddown_col<TILE, 4, TG>,
+            k_moddown_col<TILE, 8, TG>, TILE, TILE >> 2};
+}
+using KsKerns = SetKerns<KsArgs, const sf_barrett*, const u64*, const u64*, uint32_t, const double*, const double*,
+                         int, const double*>;
+template <int TILE>
+static KsKerns ksKerns() {
+    return {k_ntt_ks<2, TILE, 1>, k_ntt_ks<2, TILE, 2>, k_ntt_ks<2, TILE, 4>, k_ntt_ks<2, TILE, 8>, TILE, TILE >> 2};
+}
+// (four element-wise argument sets fill the 4 KB of kernel arguments: no k8)
+template <class A>
+using YKerns = SetKerns<A, const sf_barrett*, uint32_t>;
+template <int OP>
+static YKerns<EwArgs> ewKerns() {
+    return {k_ew<OP, 1>, k_ew<OP, 2>, k_ew<OP, 4>, nullptr, 0, kThreads};
+}
+static YKerns<WsumArgs> wsumKerns() { return {k_lin_wsum<1>, k_lin_wsum<2>, k_lin_wsum<4>, nullptr, 0, kThreads}; }
+static YKerns<AutArgs> autKerns() { return {k_automorph<1>, k_automorph<2>, k_automorph<4>, nullptr, 0, kThreads}; }
+static YKerns<KsInnerArgs> ksInnerKerns() {
+    return {k_ks_inner<1>, k_ks_inner<2>, k_ks_inner<4>, nullptr, 0, kThreads};
+}
+// the fused conversion + COL passes (nttRows), at both tiles and target-group sizes
+static const std::vector<NttKerns>& fusedColKerns(bool moddown) {
+    static const std::vector<NttKerns> up = {modupColKerns<kNttTile, kModupTg>(), modupColKerns<kNttSmallTile, kModupTg>(),
+                                             modupColKerns<kNttTile, 2>(), modupColKerns<kNttSmallTile, 2>()};
+    static const std::vector<NttKerns> down = {moddownColKerns<kNttTile, kModdownTg>(),
+                                               moddownColKerns<kNttSmallTile, kModdownTg>()};
+    return moddown ? down : up;
+}
+
+// the twiddle tables of an NTT direction
+struct NttTables {
     const u64 *tw, *twS;
     const double *twD, *rowD;
 };
-template <int NG>
-using KsKernN = void (*)(ArgSet<KsArgs, NG>, const sf_barrett*, const u64*, const u64*, uint32_t, const double*,
-                         const double*, int, const double*);
-struct KsPay {
-    KsArgs a;
-    uint32_t rows;
-    dim3 g;
-    int threads, useFp;
-    KsKernN<2> k2;
-    KsKernN<4> k4;
-    KsKernN<8> k8;
+// What a merged launch reads of a head of the row-set kernels (STK_NTT,
+// STK_KS): its argument set, grid and family.
+template <class Kerns>
+struct SetPay {
+    typename Kerns::Args a;
+    uint32_t rows, gx;
+    int useFp;
+    Kerns kerns;
+    NttTables t;
 };
 using ConvKern = void (*)(ConvJobs, const sf_barrett*, const double*, uint32_t);
 struct ConvPay {
@@ -3939,27 +4021,75 @@ struct MdrsPay {
 };
 using MdrsKern = void (*)(MdrsArgs, const sf_barrett*, const double*, uint32_t);
 
-// up to this many heads become one launch (the ArgSet<T, 4> kernels)
+// up to this many heads become one launch (the ArgSet<T, 8> kernels)
 constexpr int kMergeMax = 8;
 
-// The row-group kernels (k_ntt, k_ntt_ks): the heads' argument sets in one
-// ArgSet<T, NG> (NG = 2 or 4), rows concatenated -- or alternating when every
-// set has the same row count and fills the NG slots.
-template <class T, int NG, class F>
+// The row-set kernels (k_ntt and its fused column passes, k_ntt_ks): cnt
+// argument sets in the ArgSet<T, NG> that holds them (NG = 1, 2, 4 or 8; a
+// group that does not fill it is padded with its last set, which gets no
+// rows), rows concatenated -- or alternating when every set has the same row
+// count and they fill the NG slots.  launch(S, total grid rows).
+template <class T, class F>
 static void launchSets(const T* const* a, const uint32_t* rows, int cnt, F&& launch) {
-    ArgSet<T, NG> S;
-    uint32_t total = 0;
-    bool equal = true;
-    for (int i = 0; i < NG; ++i) {
-        S.a[i] = *a[std::min(i, cnt - 1)];
-        S.start[i] = total;
-        if (i < cnt) {
-            total += rows[i];
-            equal = equal && rows[i] == rows[0];
+    withWidth(cnt, [&](auto ng) {
+        constexpr int NG = decltype(ng)::value;
+        ArgSet<T, NG> S;
+        uint32_t total = 0;
+        bool equal = true;
+        for (int i = 0; i < NG; ++i) {
+            S.a[i] = *a[std::min(i, cnt - 1)];
+            S.start[i] = total;
+            if (i < cnt) {
+                total += rows[i];
+                equal = equal && rows[i] == rows[0];
+            }
         }
-    }
-    S.inter = equal && cnt == NG;
-    launch(S, total);
+        S.inter = NG > 1 && equal && cnt == NG;
+        launch(S, total);
+    });
+}
+static NttTables nttTables(const sfp_dev* d, int inverse) {
+    return inverse ? NttTables{d->ipsi, d->ipsiS, d->ipsiD, d->irowD} : NttTables{d->psi, d->psiS, d->psiD, d->rowD};
+}
+// Whether a launch of `rows` rows takes the kNttSmallTile kernels: few rows
+// (up to maxRows), and at least two columns per COL tile, i.e. n <= 2^17.
+static bool nttSmallTile(const sfp_dev* d, uint32_t rows, uint32_t maxRows) {
+    return rows <= maxRows && d->n <= (uint32_t)kNttSmallTile * 128u;
+}
+// maxRows of k_ntt_ks (k_ntt's is the knob SFHE_NTT_T1K_ROWS, which this does not follow)
+constexpr uint32_t kKsT1kRows = 64;
+template <int NG>
+static void launchSet(sfp_dev* d, hipStream_t s, const NttKerns& K, dim3 g, const RowGroupSet<NG>& S, int fp,
+                      const NttTables& t) {
+    hipLaunchKernelGGL(K.get<NG>(), g, dim3(K.threads), 0, s, S, d->bar, t.tw, t.twS, d->ninv, d->ninvS, d->logn, t.twD,
+                       d->qinvD, d->ninvD, d->ninvQ, fp, t.rowD);
+}
+template <int NG>
+static void launchSet(sfp_dev* d, hipStream_t s, const KsKerns& K, dim3 g, const ArgSet<KsArgs, NG>& S, int fp,
+                      const NttTables& t) {
+    hipLaunchKernelGGL(K.get<NG>(), g, dim3(K.threads), 0, s, S, d->bar, t.tw, t.twS, d->logn, t.twD, d->qinvD, fp,
+                       t.rowD);
+}
+static int nttFp();
+// One launch of family K over the cnt argument sets a[0..cnt) of rows[]
+// grid rows each, issued or (stacked region) recorded.  A single set of
+// merge class cls != 0 takes its payload along, so that stackFlush may issue
+// it with other lanes' heads as one launch (mergeSets).
+template <class Kerns>
+static void issueSets(sfp_dev* d, uint32_t cls, const Kerns& K, const typename Kerns::Args* const* a,
+                      const uint32_t* rows, int cnt, const NttTables& t) {
+    const int fp = nttFp();
+    const uint32_t gx = d->n / (uint32_t)K.tile;
+    launchSets(a, rows, cnt, [&](const auto& S, uint32_t total) {
+        StackRec r;
+        r.go = [=](hipStream_t s_) { launchSet(d, s_, K, dim3(gx, total), S, fp, t); };
+        if (cls && cnt == 1 && K.k2 && d->stackOn) {
+            r.cls = cls;
+            r.key = stkKey((const void*)K.k1, gx, (uint32_t)K.threads);
+            r.pay = std::make_shared<SetPay<Kerns>>(SetPay<Kerns>{*a[0], rows[0], gx, fp, K, t});
+        }
+        issueRec(d, std::move(r));
+    });
 }
 
 // grid.y arg-set kernels (k_ew, k_automorph, k_lin_wsum, k_ks_inner): the
@@ -3973,10 +4103,9 @@ struct YPayBase {
 template <class Args>
 struct YPay : YPayBase {
     Args a;
-    void (*k2)(ArgSet<Args, 2>, const sf_barrett*, uint32_t);
-    void (*k4)(ArgSet<Args, 4>, const sf_barrett*, uint32_t);
-    template <int NG, class K>
-    void go(sfp_dev* d, hipStream_t s, const YPayBase* const* h, int cnt, K k) const {
+    YKerns<Args> kerns;
+    template <int NG>
+    void go(sfp_dev* d, hipStream_t s, const YPayBase* const* h, int cnt) const {
         ArgSet<Args, NG> S;
         uint32_t gx = 0;
         for (int i = 0; i < NG; ++i) {
@@ -3986,36 +4115,56 @@ struct YPay : YPayBase {
             gx = std::max(gx, o.g.x);
         }
         S.inter = 0;
-        hipLaunchKernelGGL(k, dim3(gx, cnt), dim3(kThreads), 0, s, S, d->bar, d->logn);
+        hipLaunchKernelGGL(kerns.template get<NG>(), dim3(gx, cnt), dim3(kerns.threads), 0, s, S, d->bar, d->logn);
     }
     void launchMany(sfp_dev* d, hipStream_t s, const YPayBase* const* h, int cnt) const override {
         if (cnt == 2)
-            go<2>(d, s, h, cnt, k2);
+            go<2>(d, s, h, cnt);
         else
-            go<4>(d, s, h, cnt, k4);
+            go<4>(d, s, h, cnt);
     }
 };
 template <class Args>
-static void issueY(sfp_dev* d, void (*k1)(ArgSet<Args, 1>, const sf_barrett*, uint32_t),
-                   void (*k2)(ArgSet<Args, 2>, const sf_barrett*, uint32_t),
-                   void (*k4)(ArgSet<Args, 4>, const sf_barrett*, uint32_t), dim3 g, const Args& a) {
+static void issueY(sfp_dev* d, const YKerns<Args>& K, dim3 g, const Args& a) {
     ArgSet<Args, 1> S;
     S.a[0] = a;
     S.start[0] = 0;
     S.inter = 0;
     StackRec r;
-    r.go = [=](hipStream_t s_) { hipLaunchKernelGGL(k1, g, dim3(kThreads), 0, s_, S, d->bar, d->logn); };
+    r.go = [=](hipStream_t s_) { hipLaunchKernelGGL(K.k1, g, dim3(K.threads), 0, s_, S, d->bar, d->logn); };
     if (d->stackOn) {
         auto P = std::make_shared<YPay<Args>>();
         P->a = a;
-        P->k2 = k2;
-        P->k4 = k4;
+        P->kerns = K;
         P->g = g;
         r.cls = STK_Y;
-        r.key = stkKey((const void*)k1, 0, 0);
+        r.key = stkKey((const void*)K.k1, 0, 0);
         r.pay = std::move(P);
     }
     issueRec(d, std::move(r));
+}
+
+// stackMerge for the row-set kernels: the heads' sets as one launchSets launch
+// of the family's form at that width -- given one grid.x and integer / FP64
+// choice, at most 65 535 grid rows in all, and such a form.
+template <class Kerns>
+static bool mergeSets(sfp_dev* d, const StackRec* const* h, int cnt, hipStream_t s, bool check) {
+    const SetPay<Kerns>* P[kMergeMax];
+    const typename Kerns::Args* A[kMergeMax];
+    uint32_t rows[kMergeMax], total = 0;
+    for (int i = 0; i < cnt; ++i) {
+        P[i] = static_cast<const SetPay<Kerns>*>(h[i]->pay.get());
+        A[i] = &P[i]->a;
+        rows[i] = P[i]->rows;
+        total += rows[i];
+        if (P[i]->gx != P[0]->gx || P[i]->useFp != P[0]->useFp) return false;
+    }
+    const SetPay<Kerns>& B = *P[0];
+    if (total > 65535u || !withWidth(cnt, [&](auto ng) { return B.kerns.form(ng) != nullptr; })) return false;
+    if (check) return true;
+    launchSets(A, rows, cnt,
+               [&](const auto& S, uint32_t tot) { launchSet(d, s, B.kerns, dim3(B.gx, tot), S, B.useFp, B.t); });
+    return true;
 }
 
 // Issue the heads h[0..cnt) (2 <= cnt <= kMergeMax, one class and key) as one
@@ -4024,78 +4173,10 @@ static void issueY(sfp_dev* d, void (*k1)(ArgSet<Args, 1>, const sf_barrett*, ui
 static bool stackMerge(sfp_dev* d, const StackRec* const* h, int cnt, hipStream_t s, bool check) {
     auto pay = [&](int i) { return h[i]->pay.get(); };
     switch (h[0]->cls) {
-        case STK_NTT: {
-            const NttPay* P[kMergeMax];
-            const RowGroup* G[kMergeMax];
-            uint32_t rows[kMergeMax], total = 0;
-            for (int i = 0; i < cnt; ++i) {
-                P[i] = static_cast<const NttPay*>(pay(i));
-                G[i] = &P[i]->G;
-                rows[i] = P[i]->rows;
-                total += rows[i];
-                if (P[i]->g.x != P[0]->g.x || P[i]->useFp != P[0]->useFp) return false;
-            }
-            if (total > 65535u || !(cnt == 2 ? (bool)P[0]->k2 : cnt <= 4 ? (bool)P[0]->k4 : (bool)P[0]->k8))
-                return false;
-            if (check) return true;
-            const NttPay& A = *P[0];
-            auto launch = [&](const auto& S, uint32_t tot) {
-                using SetT = std::decay_t<decltype(S)>;
-                constexpr int NG = sizeof(SetT::a) / sizeof(RowGroup);
-                NttKernN<NG> k;
-                if constexpr (NG == 2)
-                    k = A.k2;
-                else if constexpr (NG == 4)
-                    k = A.k4;
-                else
-                    k = A.k8;
-                hipLaunchKernelGGL(k, dim3(A.g.x, tot), dim3(A.threads), 0, s, S, d->bar, A.tw, A.twS, d->ninv,
-                                   d->ninvS, d->logn, A.twD, d->qinvD, d->ninvD, d->ninvQ, A.useFp, A.rowD);
-            };
-            if (cnt == 2)
-                launchSets<RowGroup, 2>(G, rows, cnt, launch);
-            else if (cnt <= 4)
-                launchSets<RowGroup, 4>(G, rows, cnt, launch);
-            else
-                launchSets<RowGroup, 8>(G, rows, cnt, launch);
-            return true;
-        }
-        case STK_KS: {
-            const KsPay* P[kMergeMax];
-            const KsArgs* A[kMergeMax];
-            uint32_t rows[kMergeMax], total = 0;
-            for (int i = 0; i < cnt; ++i) {
-                P[i] = static_cast<const KsPay*>(pay(i));
-                A[i] = &P[i]->a;
-                rows[i] = P[i]->rows;
-                total += rows[i];
-                if (P[i]->g.x != P[0]->g.x || P[i]->useFp != P[0]->useFp) return false;
-            }
-            if (total > 65535u || !(cnt == 2 ? (bool)P[0]->k2 : cnt <= 4 ? (bool)P[0]->k4 : (bool)P[0]->k8))
-                return false;
-            if (check) return true;
-            const KsPay& B = *P[0];
-            auto launch = [&](const auto& S, uint32_t tot) {
-                using SetT = std::decay_t<decltype(S)>;
-                constexpr int NG = sizeof(SetT::a) / sizeof(KsArgs);
-                KsKernN<NG> k;
-                if constexpr (NG == 2)
-                    k = B.k2;
-                else if constexpr (NG == 4)
-                    k = B.k4;
-                else
-                    k = B.k8;
-                hipLaunchKernelGGL(k, dim3(B.g.x, tot), dim3(B.threads), 0, s, S, d->bar, d->psi, d->psiS, d->logn,
-                                   d->psiD, d->qinvD, B.useFp, d->rowD);
-            };
-            if (cnt == 2)
-                launchSets<KsArgs, 2>(A, rows, cnt, launch);
-            else if (cnt <= 4)
-                launchSets<KsArgs, 4>(A, rows, cnt, launch);
-            else
-                launchSets<KsArgs, 8>(A, rows, cnt, launch);
-            return true;
-        }
+        case STK_NTT:
+            return mergeSets<NttKerns>(d, h, cnt, s, check);
+        case STK_KS:
+            return mergeSets<KsKerns>(d, h, cnt, s, check);
         case STK_CONV: {
             const ConvPay* P[kMergeMax];
             uint32_t jobs = 0, gz = 0;
@@ -4151,7 +4232,7 @@ static bool stackMerge(sfp_dev* d, const StackRec* const* h, int cnt, hipStream_
     }
 }
 
-// Issue one launch (or a merged pair) on s, bracketed by HIP events when its
+// Issue one launch (or one merged group's) on s, bracketed by HIP events when its
 // family is being timed (sfp_prof_set) and this launch is a sampled one.
 template <class F>
 static void stackTimed(sfp_dev* d, hipStream_t s, uint32_t fam, double bytes, F&& go) {
@@ -4848,54 +4929,18 @@ static void nttRows(sfp_dev* d, const RowGroup& G0, int inverse, int passes = 3)
         checkLaunch(d, "ntt");
         return;
     }
-    const u64* tw = inverse ? d->ipsi : d->psi;
-    const u64* twS = inverse ? d->ipsiS : d->psiS;
-    const double* twD = inverse ? d->ipsiD : d->psiD;
-    const double* rowD = inverse ? d->irowD : d->rowD;
     // Launches over few rows are latency-bound (a one-limb pass is one tile
     // round trip per block: ~1.5 us load, ~1 us per register round, tools/
     // microbench with SFHE_NTT_TRACE): up to SFHE_NTT_T1K_ROWS rows (default
-    // 64) they run 1024-word tiles -- twice the blocks, half the work each;
-    // needs >= 2 columns per COL tile, i.e. n <= 2^17.  Measured on the metric
-    // sort: NTT 47.9 -> 46.0 ms, wall 58.1 -> 57.5 ms.
-    const bool t1k = rows <= nttT1kRows() && d->n <= (uint32_t)kNttSmallTile * 128u;
-    dim3 g(d->n / (uint32_t)(t1k ? kNttSmallTile : kNttTile), rows);
+    // 64) they run 1024-word tiles -- twice the blocks, half the work each.
+    // Measured on the metric sort: NTT 47.9 -> 46.0 ms, wall 58.1 -> 57.5 ms.
+    const bool t1k = nttSmallTile(d, rows, nttT1kRows());
     uint32_t gridRows = rows;  // (k_modup_col: grid rows are groups of target rows)
     int npass = 0;
-    // kern2 / kern4: the same pass over two / four row groups (merged launches), or null
-    auto pass = [&](auto kern, NttKern2 kern2, NttKern4 kern4, NttKern8 kern8, int threads) {
+    auto pass = [&](const NttKerns& K) {
         if (!((passes >> npass++) & 1)) return;
-        timedLaunch(d, SFP_FAM_NTT, bytes, [&] {
-            RowGroupSet<1> GS;
-            GS.a[0] = G;
-            GS.start[0] = 0;
-            GS.inter = 0;
-            const int fp = nttFp();
-            StackRec r;
-            r.go = [=](hipStream_t s_) {
-                hipLaunchKernelGGL(kern, g, dim3(threads), 0, s_, GS, d->bar, tw, twS, d->ninv, d->ninvS, d->logn,
-                                   twD, d->qinvD, d->ninvD, d->ninvQ, fp, rowD);
-            };
-            if (kern2 && d->stackOn) {
-                auto P = std::make_shared<NttPay>();
-                P->G = G;
-                P->rows = gridRows;
-                P->g = g;
-                P->threads = threads;
-                P->useFp = fp;
-                P->k2 = kern2;
-                P->k4 = kern4;
-                P->k8 = kern8;
-                P->tw = tw;
-                P->twS = twS;
-                P->twD = twD;
-                P->rowD = rowD;
-                r.cls = STK_NTT;
-                r.key = stkKey((const void*)kern, g.x, (uint32_t)threads);
-                r.pay = std::move(P);
-            }
-            issueRec(d, std::move(r));
-        });
+        const RowGroup* a = &G;
+        timedLaunch(d, SFP_FAM_NTT, bytes, [&] { issueSets(d, STK_NTT, K, &a, &gridRows, 1, nttTables(d, inverse)); });
     };
     const int L = rows < (uint32_t)kNttSmallRows ? 2 : 3;  // (see kNttSmallRows)
     static const bool modupCol = [] {  // SFHE_MODUP_COL=0: k_ntt<..., CONV> (one target per block; A/B)
@@ -4916,38 +4961,31 @@ static void nttRows(sfp_dev* d, const RowGroup& G0, int inverse, int passes = 3)
         const char* v = std::getenv("SFHE_MODUP_TG_SMALL");
         return v ? (uint32_t)std::atoi(v) : 512u;
     }();
-    // The LE = 2 pass pair at one tile size.  (Each specialisation is named in
-    // a call of its own: named only inside a conditional expression, the
-    // device code of some was never emitted -- "Cannot find Symbol" at launch.)
+    // The LE = 2 pass pair at one tile size
     auto le2Passes = [&](auto tileC) {
         constexpr int TL = decltype(tileC)::value;
-        constexpr int TH = TL >> 2;
         if (inverse) {
-            pass(k_ntt<true, false, 2, TL>, k_ntt<true, false, 2, TL, 2>, k_ntt<true, false, 2, TL, 4>, k_ntt<true, false, 2, TL, 8>, TH);
-            pass(k_ntt<true, true, 2, TL>, k_ntt<true, true, 2, TL, 2>, k_ntt<true, true, 2, TL, 4>, k_ntt<true, true, 2, TL, 8>, TH);
+            pass(nttKerns<true, false, 2, TL>());
+            pass(nttKerns<true, true, 2, TL>());
             return;
         }
         if (G.md) {
             constexpr int TG = kModdownTg;
-            g.y = gridRows = G.P * ((G.R + TG - 1) / TG);
-            pass(k_moddown_col<TL, 1, TG>, k_moddown_col<TL, 2, TG>, k_moddown_col<TL, 4, TG>, k_moddown_col<TL, 8, TG>, TH);
+            gridRows = G.P * ((G.R + TG - 1) / TG);
+            pass(moddownColKerns<TL, TG>());
         } else if (modupColPass) {
             constexpr int TG = kModupTg;
-            const bool tg2 = G.P * ((G.R + TG - 1) / TG) * g.x < tgSmall;
+            const bool tg2 = G.P * ((G.R + TG - 1) / TG) * (d->n / (uint32_t)TL) < tgSmall;
             const int tg = tg2 ? 2 : TG;
-            g.y = gridRows = G.P * ((G.R + tg - 1) / tg);
-            if (tg2)
-                pass(k_modup_col<TL, 1, 2>, k_modup_col<TL, 2, 2>, k_modup_col<TL, 4, 2>, k_modup_col<TL, 8, 2>, TH);
-            else
-                pass(k_modup_col<TL, 1, TG>, k_modup_col<TL, 2, TG>, k_modup_col<TL, 4, TG>, k_modup_col<TL, 8, TG>, TH);
+            gridRows = G.P * ((G.R + tg - 1) / tg);
+            pass(tg2 ? modupColKerns<TL, 2>() : modupColKerns<TL, TG>());
         } else if (G.cy) {  // ModUpPlan: the conversion in the COL pass's prologue, one target per block
-            pass(k_ntt<false, true, 2, TL, 1, true>, k_ntt<false, true, 2, TL, 2, true>,
-                 k_ntt<false, true, 2, TL, 4, true>, k_ntt<false, true, 2, TL, 8, true>, TH);
+            pass(nttKerns<false, true, 2, TL, true>());
         } else {
-            pass(k_ntt<false, true, 2, TL>, k_ntt<false, true, 2, TL, 2>, k_ntt<false, true, 2, TL, 4>, k_ntt<false, true, 2, TL, 8>, TH);
+            pass(nttKerns<false, true, 2, TL>());
         }
-        g.y = gridRows = rows;
-        pass(k_ntt<false, false, 2, TL>, k_ntt<false, false, 2, TL, 2>, k_ntt<false, false, 2, TL, 4>, k_ntt<false, false, 2, TL, 8>, TH);
+        gridRows = rows;
+        pass(nttKerns<false, false, 2, TL>());
     };
     constexpr int T = kNttTile;
     if (t1k) {
@@ -4955,11 +4993,11 @@ static void nttRows(sfp_dev* d, const RowGroup& G0, int inverse, int passes = 3)
     } else if (L == 2) {
         le2Passes(std::integral_constant<int, T>{});
     } else if (!inverse) {  // kNttSmallRows rows or more: single-group LE = 3 kernels
-        pass(k_ntt<false, true, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
-        pass(k_ntt<false, false, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
+        pass(nttKerns<false, true, 3, T>());
+        pass(nttKerns<false, false, 3, T>());
     } else {
-        pass(k_ntt<true, false, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
-        pass(k_ntt<true, true, 3, T>, NttKern2{}, NttKern4{}, NttKern8{}, T >> 3);
+        pass(nttKerns<true, false, 3, T>());
+        pass(nttKerns<true, true, 3, T>());
     }
     checkLaunch(d, "ntt");
 }
@@ -5113,63 +5151,37 @@ void sfp_graph_launch(sfp_dev* d, sfp_graph* g) {
 size_t sfp_graph_nodes(const sfp_graph* g) { return g ? g->nodes : 0; }
 
 // The family of a kernel (graph timing): every instantiation the launch
-// sites issue; anything else is SFP_FAM_COUNT ("other").
-template <bool I, bool C, int LE, int T>
-static void addNtt(std::unordered_map<const void*, uint32_t>& m, bool merged) {
-    m[(const void*)k_ntt<I, C, LE, T>] = SFP_FAM_NTT;
-    if (merged) {
-        m[(const void*)k_ntt<I, C, LE, T, 2>] = SFP_FAM_NTT;
-        m[(const void*)k_ntt<I, C, LE, T, 4>] = SFP_FAM_NTT;
-        m[(const void*)k_ntt<I, C, LE, T, 8>] = SFP_FAM_NTT;
-    }
-}
-template <int LE, int T>
-static void addNttAll(std::unordered_map<const void*, uint32_t>& m, bool merged) {
-    addNtt<false, true, LE, T>(m, merged);
-    addNtt<false, false, LE, T>(m, merged);
-    addNtt<true, true, LE, T>(m, merged);
-    addNtt<true, false, LE, T>(m, merged);
-}
+// sites issue, from the families' descriptors at the tiles and target-group
+// sizes those sites use; anything else is SFP_FAM_COUNT ("other").
 static uint32_t kernelFamily(const void* f) {
     static const std::unordered_map<const void*, uint32_t> fam = [] {
         std::unordered_map<const void*, uint32_t> m;
-        addNttAll<2, kNttTile>(m, true);
-        for (const void* k : {(const void*)k_ntt<false, true, 2, kNttTile, 1, true>,
-                              (const void*)k_ntt<false, true, 2, kNttTile, 2, true>,
-                              (const void*)k_ntt<false, true, 2, kNttTile, 4, true>,
-                              (const void*)k_ntt<false, true, 2, kNttTile, 8, true>,
-                              (const void*)k_ntt<false, true, 2, kNttSmallTile, 1, true>, (const void*)k_ntt<false, true, 2, kNttSmallTile, 2, true>,
-                              (const void*)k_ntt<false, true, 2, kNttSmallTile, 4, true>, (const void*)k_ntt<false, true, 2, kNttSmallTile, 8, true>})
-            m[k] = SFP_FAM_NTT;  // (the ModUp COL pass with its conversion)
-        for (const void* k : {(const void*)k_modup_col<kNttTile, 1, kModupTg>, (const void*)k_modup_col<kNttTile, 2, kModupTg>,
-                              (const void*)k_modup_col<kNttTile, 4, kModupTg>, (const void*)k_modup_col<kNttTile, 8, kModupTg>,
-                              (const void*)k_modup_col<kNttSmallTile, 1, kModupTg>, (const void*)k_modup_col<kNttSmallTile, 2, kModupTg>,
-                              (const void*)k_modup_col<kNttSmallTile, 4, kModupTg>, (const void*)k_modup_col<kNttSmallTile, 8, kModupTg>,
-                              (const void*)k_modup_col<kNttTile, 1, 2>, (const void*)k_modup_col<kNttTile, 2, 2>,
-                              (const void*)k_modup_col<kNttTile, 4, 2>, (const void*)k_modup_col<kNttTile, 8, 2>,
-                              (const void*)k_modup_col<kNttSmallTile, 1, 2>, (const void*)k_modup_col<kNttSmallTile, 2, 2>,
-                              (const void*)k_modup_col<kNttSmallTile, 4, 2>, (const void*)k_modup_col<kNttSmallTile, 8, 2>})
-            m[k] = SFP_FAM_NTT;
-        for (const void* k : {(const void*)k_moddown_col<kNttTile, 1, kModdownTg>, (const void*)k_moddown_col<kNttTile, 2, kModdownTg>,
-                              (const void*)k_moddown_col<kNttTile, 4, kModdownTg>, (const void*)k_moddown_col<kNttTile, 8, kModdownTg>,
-                              (const void*)k_moddown_col<kNttSmallTile, 1, kModdownTg>, (const void*)k_moddown_col<kNttSmallTile, 2, kModdownTg>,
-                              (const void*)k_moddown_col<kNttSmallTile, 4, kModdownTg>, (const void*)k_moddown_col<kNttSmallTile, 8, kModdownTg>})
-            m[k] = SFP_FAM_NTT;
-        addNttAll<2, kNttSmallTile>(m, true);
-        addNttAll<3, kNttTile>(m, false);
+        auto add = [&m](const auto& K, uint32_t family) {
+            for (int ng : {1, 2, 4, 8})
+                if (K.form(ng)) m[K.form(ng)] = family;
+        };
+        auto tile = [&](auto tileC) {
+            constexpr int TL = decltype(tileC)::value;
+            for (const NttKerns& K : {nttKerns<false, true, 2, TL>(), nttKerns<false, false, 2, TL>(),
+                                      nttKerns<true, true, 2, TL>(), nttKerns<true, false, 2, TL>(),
+                                      nttKerns<false, true, 2, TL, true>()})  // (the last: ModUp's COL pass with its conversion)
+                add(K, SFP_FAM_NTT);
+            add(ksKerns<TL>(), SFP_FAM_NTTKS);
+        };
+        tile(std::integral_constant<int, kNttTile>{});
+        tile(std::integral_constant<int, kNttSmallTile>{});
+        for (const NttKerns& K : {nttKerns<false, true, 3, kNttTile>(), nttKerns<false, false, 3, kNttTile>(),
+                                  nttKerns<true, true, 3, kNttTile>(), nttKerns<true, false, 3, kNttTile>()})
+            add(K, SFP_FAM_NTT);
+        for (bool md : {false, true})
+            for (const NttKerns& K : fusedColKerns(md)) add(K, SFP_FAM_NTT);
         for (const void* k : {(const void*)k_convf<13>, (const void*)k_convf<16>, (const void*)k_convf<kMaxConvSrc>,
                               (const void*)k_conv, (const void*)k_mdrsf<13, true>, (const void*)k_mdrsf<16, true>,
                               (const void*)k_mdrsf<kMaxConvSrc, true>, (const void*)k_mdrsf<13>,
                               (const void*)k_mdrsf<16>, (const void*)k_mdrsf<kMaxConvSrc>, (const void*)k_conv_mdrs,
                               (const void*)k_mdrsi<16>, (const void*)k_mdrsi<kMaxConvSrc>})
             m[k] = SFP_FAM_CONV;
-        for (const void* k : {(const void*)k_ks_inner<1>, (const void*)k_ks_inner<2>, (const void*)k_ks_inner<4>})
-            m[k] = SFP_FAM_KSINNER;
-        for (const void* k : {(const void*)k_ntt_ks<2, 1024>, (const void*)k_ntt_ks<2, 1024, 2>,
-                              (const void*)k_ntt_ks<2, 1024, 4>, (const void*)k_ntt_ks<2, 1024, 8>,
-                              (const void*)k_ntt_ks<2, kNttTile>, (const void*)k_ntt_ks<2, kNttTile, 2>,
-                              (const void*)k_ntt_ks<2, kNttTile, 4>, (const void*)k_ntt_ks<2, kNttTile, 8>})
-            m[k] = SFP_FAM_NTTKS;
+        add(ksInnerKerns(), SFP_FAM_KSINNER);
         return m;
     }();
     auto it = fam.find(f);
@@ -5192,22 +5204,12 @@ static double fusedColRows(const void* arg, bool moddown) {
     }
     return r;
 }
-template <int NG>
-static bool isFusedCol(const void* f, bool md) {
-    return md ? (f == (const void*)k_moddown_col<kNttTile, NG, kModdownTg> ||
-                 f == (const void*)k_moddown_col<kNttSmallTile, NG, kModdownTg>)
-              : (f == (const void*)k_modup_col<kNttTile, NG, kModupTg> || f == (const void*)k_modup_col<kNttSmallTile, NG, kModupTg> ||
-                 f == (const void*)k_modup_col<kNttTile, NG, 2> || f == (const void*)k_modup_col<kNttSmallTile, NG, 2>);
-}
 static double nttNodeRows(const hipKernelNodeParams& kp) {
-    const void* f = kp.func;
     if (kp.kernelParams) {
-        for (bool md : {false, true}) {
-            if (isFusedCol<1>(f, md)) return fusedColRows<1>(kp.kernelParams[0], md);
-            if (isFusedCol<2>(f, md)) return fusedColRows<2>(kp.kernelParams[0], md);
-            if (isFusedCol<4>(f, md)) return fusedColRows<4>(kp.kernelParams[0], md);
-            if (isFusedCol<8>(f, md)) return fusedColRows<8>(kp.kernelParams[0], md);
-        }
+        for (bool md : {false, true})
+            for (const NttKerns& K : fusedColKerns(md))
+                if (const int w = K.widthOf(kp.func))
+                    return withWidth(w, [&](auto ng) { return fusedColRows<decltype(ng)::value>(kp.kernelParams[0], md); });
     }
     return (double)kp.gridDim.y;
 }
@@ -5247,15 +5249,9 @@ static double ksNodeBytesNG(const void* arg, uint32_t gridY, uint32_t n) {
     return b;
 }
 static double ksNodeBytes(const hipKernelNodeParams& kp, uint32_t n) {
-    const void* f = kp.func;
     if (!kp.kernelParams) return 0;
-    if (f == (const void*)k_ntt_ks<2, 1024> || f == (const void*)k_ntt_ks<2, kNttTile>)
-        return ksNodeBytesNG<1>(kp.kernelParams[0], kp.gridDim.y, n);
-    if (f == (const void*)k_ntt_ks<2, 1024, 2> || f == (const void*)k_ntt_ks<2, kNttTile, 2>)
-        return ksNodeBytesNG<2>(kp.kernelParams[0], kp.gridDim.y, n);
-    if (f == (const void*)k_ntt_ks<2, 1024, 4> || f == (const void*)k_ntt_ks<2, kNttTile, 4>)
-        return ksNodeBytesNG<4>(kp.kernelParams[0], kp.gridDim.y, n);
-    return ksNodeBytesNG<8>(kp.kernelParams[0], kp.gridDim.y, n);
+    const int w = std::max(ksKerns<kNttSmallTile>().widthOf(kp.func), ksKerns<kNttTile>().widthOf(kp.func));
+    return withWidth(w, [&](auto ng) { return ksNodeBytesNG<decltype(ng)::value>(kp.kernelParams[0], kp.gridDim.y, n); });
 }
 
 int sfp_graph_family_time(sfp_dev* d, sfp_graph* g, uint32_t fam, int reps, double* ms, uint64_t* launches,
@@ -5346,7 +5342,7 @@ static void ew(sfp_dev* d, u64* out, const u64* a, const u64* b, const u64* c, s
     const size_t pairs = ((size_t)m.count * d->n) / 2;
     EwArgs A{out, a, b, c, m, {}};
     A.k = ka;
-    issueY<EwArgs>(d, k_ew<OP, 1>, k_ew<OP, 2>, k_ew<OP, 4>, dim3(ewGrid(pairs)), A);
+    issueY<EwArgs>(d, ewKerns<OP>(), dim3(ewGrid(pairs)), A);
     checkLaunch(d, "elementwise");
 }
 
@@ -5410,7 +5406,7 @@ void sfp_lin_wsum(sfp_dev* d, uint64_t* out, const uint64_t* const* ins, const u
     for (uint32_t j = 0; j < nin; ++j) pl.p[j] = ins[j];
     const u64* dk = (const u64*)ringPut(d, k, (size_t)nin * m.count * 8);
     const size_t total = (size_t)m.count * d->n;
-    issueY<WsumArgs>(d, k_lin_wsum<1>, k_lin_wsum<2>, k_lin_wsum<4>, dim3(ewGrid(total)), WsumArgs{out, pl, dk, nin, m});
+    issueY<WsumArgs>(d, wsumKerns(), dim3(ewGrid(total)), WsumArgs{out, pl, dk, nin, m});
     checkLaunch(d, "lin_wsum");
 }
 
@@ -5508,7 +5504,7 @@ void sfp_mac_plain(sfp_dev* d, uint64_t* out, const uint64_t* const* a, const ui
 
 void sfp_automorph(sfp_dev* d, uint64_t* out, const uint64_t* in, uint32_t g, sfp_limbs m) {
     const size_t total = (size_t)m.count * d->n;
-    issueY<AutArgs>(d, k_automorph<1>, k_automorph<2>, k_automorph<4>, dim3(ewGrid(total)), AutArgs{out, in, g, m.count});
+    issueY<AutArgs>(d, autKerns(), dim3(ewGrid(total)), AutArgs{out, in, g, m.count});
     checkLaunch(d, "automorph");
 }
 
@@ -5683,49 +5679,21 @@ static bool nttRowsMulti(sfp_dev* d, const RowGroup* G, int cnt, int inverse) {
         record(d, "ntt (row-group sets: shape)", hipErrorInvalidValue);
         return false;
     }
-    const u64* tw = inverse ? d->ipsi : d->psi;
-    const u64* twS = inverse ? d->ipsiS : d->psiS;
-    const double* twD = inverse ? d->ipsiD : d->psiD;
-    const double* rowD = inverse ? d->irowD : d->rowD;
-    const bool t1k = total <= nttT1kRows() && d->n <= (uint32_t)kNttSmallTile * 128u;
     const double bytes = 16.0 * total * d->n;
-    const int fp = nttFp();
-    auto pass = [&](auto k2, auto k4, uint32_t tile) {
-        timedLaunch(d, SFP_FAM_NTT, bytes, [&] {
-            auto launch = [&](const auto& S, uint32_t tot) {
-                using SetT = std::decay_t<decltype(S)>;
-                constexpr int NG = sizeof(SetT::a) / sizeof(RowGroup);
-                NttKernN<NG> k;
-                if constexpr (NG == 2)
-                    k = k2;
-                else
-                    k = k4;
-                const dim3 g(d->n / tile, tot);
-                const int threads = (int)(tile >> 2);
-                StackRec r;
-                r.go = [=](hipStream_t s_) {
-                    hipLaunchKernelGGL(k, g, dim3(threads), 0, s_, S, d->bar, tw, twS, d->ninv, d->ninvS, d->logn, twD,
-                                       d->qinvD, d->ninvD, d->ninvQ, fp, rowD);
-                };
-                issueRec(d, std::move(r));
-            };
-            if (cnt == 2)
-                launchSets<RowGroup, 2>(ptr, rows, cnt, launch);
-            else
-                launchSets<RowGroup, 4>(ptr, rows, cnt, launch);
-        });
+    auto pass = [&](const NttKerns& K) {
+        timedLaunch(d, SFP_FAM_NTT, bytes, [&] { issueSets(d, STK_NONE, K, ptr, rows, cnt, nttTables(d, inverse)); });
     };
     auto passes = [&](auto tileC) {
         constexpr int TL = decltype(tileC)::value;
         if (inverse) {
-            pass(k_ntt<true, false, 2, TL, 2>, k_ntt<true, false, 2, TL, 4>, TL);
-            pass(k_ntt<true, true, 2, TL, 2>, k_ntt<true, true, 2, TL, 4>, TL);
+            pass(nttKerns<true, false, 2, TL>());
+            pass(nttKerns<true, true, 2, TL>());
         } else {
-            pass(k_ntt<false, true, 2, TL, 2>, k_ntt<false, true, 2, TL, 4>, TL);
-            pass(k_ntt<false, false, 2, TL, 2>, k_ntt<false, false, 2, TL, 4>, TL);
+            pass(nttKerns<false, true, 2, TL>());
+            pass(nttKerns<false, false, 2, TL>());
         }
     };
-    if (t1k)
+    if (nttSmallTile(d, total, nttT1kRows()))
         passes(std::integral_constant<int, kNttSmallTile>{});
     else
         passes(std::integral_constant<int, kNttTile>{});
@@ -6260,37 +6228,10 @@ static void modupInnerCore(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uin
     a.itwD = d->ipsiD;
     const uint32_t rows = ell + K;
     const size_t total = (size_t)rows * n;
-    const bool t1k = rows <= 64 && n <= 1024u * 128u;
-    timedLaunch(d, SFP_FAM_NTTKS, 8.0 * total * (3.0 * beta + (accum ? 4.0 : 2.0)), [&] {
-        ArgSet<KsArgs, 1> AS;
-        AS.a[0] = a;
-        AS.start[0] = 0;
-        AS.inter = 0;
-        const int fp = nttFp();
-        const dim3 g(n / (t1k ? 1024u : (uint32_t)kNttTile), rows);
-        const int threads = (t1k ? 1024 : kNttTile) >> 2;
-        auto k1 = t1k ? k_ntt_ks<2, 1024> : k_ntt_ks<2, kNttTile>;
-        StackRec r;
-        r.go = [=](hipStream_t s_) {
-            hipLaunchKernelGGL(k1, g, dim3(threads), 0, s_, AS, d->bar, d->psi, d->psiS, d->logn, d->psiD, d->qinvD,
-                               fp, d->rowD);
-        };
-        if (d->stackOn) {
-            auto P = std::make_shared<KsPay>();
-            P->a = a;
-            P->rows = rows;
-            P->g = g;
-            P->threads = threads;
-            P->useFp = fp;
-            P->k2 = t1k ? k_ntt_ks<2, 1024, 2> : k_ntt_ks<2, kNttTile, 2>;
-            P->k4 = t1k ? k_ntt_ks<2, 1024, 4> : k_ntt_ks<2, kNttTile, 4>;
-            P->k8 = t1k ? k_ntt_ks<2, 1024, 8> : k_ntt_ks<2, kNttTile, 8>;
-            r.cls = STK_KS;
-            r.key = stkKey((const void*)k1, g.x, (uint32_t)threads);
-            r.pay = std::move(P);
-        }
-        issueRec(d, std::move(r));
-    });
+    const KsArgs* pa = &a;
+    const KsKerns kerns = nttSmallTile(d, rows, kKsT1kRows) ? ksKerns<kNttSmallTile>() : ksKerns<kNttTile>();
+    timedLaunch(d, SFP_FAM_NTTKS, 8.0 * total * (3.0 * beta + (accum ? 4.0 : 2.0)),
+                [&] { issueSets(d, STK_KS, kerns, &pa, &rows, 1, nttTables(d, 0)); });
     checkLaunch(d, "ntt_ks");
 }
 
@@ -6336,7 +6277,7 @@ void sfp_ks_inner_fold(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_
     }
     // reads beta ext rows + 2*beta key rows, writes 2 accumulator rows, per limb
     timedLaunch(d, SFP_FAM_KSINNER, 8.0 * total * (3.0 * beta + 2.0), [&] {
-        issueY<KsInnerArgs>(d, k_ks_inner<1>, k_ks_inner<2>, k_ks_inner<4>, dim3(ewGrid(total / 2)),
+        issueY<KsInnerArgs>(d, ksInnerKerns(), dim3(ewGrid(total / 2)),
                                 KsInnerArgs{acc0, acc1, ext, extStride, key, beta, sfp_limbs{ell + K, ell, Lq, 0, 1}, keyQ0, keyRows0, fold0, fold1, foldK, 0, (const u64*)nullptr, d->kg, 0u});
     });
     checkLaunch(d, "ks_inner");
@@ -6347,7 +6288,7 @@ void sfp_ks_inner_aut(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_t
     const uint32_t keyQ0 = d->kg.rows ? d->kg.pstart : Lq, keyRows0 = d->kg.rows ? d->kg.rows : Lq + K;
     const size_t total = (size_t)(ell + K) * d->n;
     timedLaunch(d, SFP_FAM_KSINNER, 8.0 * total * (3.0 * beta + 2.0), [&] {
-        issueY<KsInnerArgs>(d, k_ks_inner<1>, k_ks_inner<2>, k_ks_inner<4>, dim3(ewGrid(total / 2)),
+        issueY<KsInnerArgs>(d, ksInnerKerns(), dim3(ewGrid(total / 2)),
                                 KsInnerArgs{acc0, acc1, ext, extStride, key, beta, sfp_limbs{ell + K, ell, Lq, 0, 1}, keyQ0, keyRows0, (const u64*)nullptr, (const u64*)nullptr, (u64)0, 0, (const u64*)nullptr, d->kg, gal});
     });
     checkLaunch(d, "ks_inner_aut");
@@ -6359,7 +6300,7 @@ void sfp_ks_inner_acc(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_t
     const size_t total = (size_t)(ell + K) * d->n;
     // reads beta ext rows + 2*beta key rows + 2 accumulator rows, writes 2, per limb
     timedLaunch(d, SFP_FAM_KSINNER, 8.0 * total * (3.0 * beta + 4.0), [&] {
-        issueY<KsInnerArgs>(d, k_ks_inner<1>, k_ks_inner<2>, k_ks_inner<4>, dim3(ewGrid(total / 2)),
+        issueY<KsInnerArgs>(d, ksInnerKerns(), dim3(ewGrid(total / 2)),
                                 KsInnerArgs{acc0, acc1, ext, extStride, key, beta, sfp_limbs{ell + K, ell, Lq, 0, 1}, keyQ0, keyRows0, (const u64*)nullptr, (const u64*)nullptr, (u64)0, 1, (const u64*)nullptr, d->kg, 0u});
     });
     checkLaunch(d, "ks_inner_acc");
@@ -6378,7 +6319,7 @@ void sfp_ks_inner_mul_aut(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint
     const size_t total = (size_t)(ell + K) * d->n;
     // reads beta ext rows + 2*beta key rows + the plaintext row (+ 2 accumulator rows), writes 2, per limb
     timedLaunch(d, SFP_FAM_KSINNER, 8.0 * total * (3.0 * beta + (accum ? 5.0 : 3.0)), [&] {
-        issueY<KsInnerArgs>(d, k_ks_inner<1>, k_ks_inner<2>, k_ks_inner<4>, dim3(ewGrid(total / 2)),
+        issueY<KsInnerArgs>(d, ksInnerKerns(), dim3(ewGrid(total / 2)),
                                 KsInnerArgs{acc0, acc1, ext, extStride, key, beta, sfp_limbs{ell + K, ell, Lq, 0, 1}, keyQ0, keyRows0, (const u64*)nullptr, (const u64*)nullptr, (u64)0, accum, pm, d->kg, gal});
     });
     checkLaunch(d, "ks_inner_mul");
@@ -7171,7 +7112,7 @@ void sfp_ks_inner_map(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_t
     if (!pm.count || !limbsOk(d, pm, "ks_inner_map")) return;
     const size_t total = (size_t)pm.count * d->n;
     timedLaunch(d, SFP_FAM_KSINNER, 8.0 * total * (3.0 * beta + (accum ? 4.0 : 2.0)), [&] {
-        issueY<KsInnerArgs>(d, k_ks_inner<1>, k_ks_inner<2>, k_ks_inner<4>, dim3(ewGrid(total / 2)),
+        issueY<KsInnerArgs>(d, ksInnerKerns(), dim3(ewGrid(total / 2)),
                                 KsInnerArgs{acc0, acc1, ext, extStride, key, beta, pm, keyQ, keyRows, (const u64*)nullptr, (const u64*)nullptr, (u64)0, accum, (const u64*)nullptr, d->kg, 0u});
     });
     checkLaunch(d, "ks_inner_map");
