@@ -29,7 +29,9 @@ extern "C" {
 /* (sfhe_decrypt_batch and sfhe_decode_counts were added at version 3: additions
  * only, no existing declaration changed, so the version stays; likewise
  * sfhe_encrypt_batch and sfhe_sample_counts, and sfhe_sorter_sort_stable,
- * sfhe_sorter_rank_stable and sfhe_tie_counts, and sfhe_const_term_counts) */
+ * sfhe_sorter_rank_stable and sfhe_tie_counts, and sfhe_const_term_counts, and
+ * the record sort: SFHE_MAX_COLUMNS, sfhe_sorter_place_many,
+ * sfhe_sorter_sort_records, sfhe_sorter_records_graph_nodes, sfhe_place_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -116,6 +118,10 @@ int sfhe_tie_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
  * rescale, and as a weighted sum followed by a rescale (SFHE_CONST_TERMS=0,
  * read per call, composes; the results are bit-identical). */
 int sfhe_const_term_counts(sfhe_ctx* c, uint64_t* merged, uint64_t* single, uint64_t* composed);
+/* since the last sfhe_op_stats reset: indicators evaluated for a multi-column placement, columns they
+ * served, giant-step sums issued through sfp_mac_plain2_cols, and through the per-column path
+ * (SFHE_PLACE_COLS=0, read per call, takes the per-column path; the results are bit-identical) */
+int sfhe_place_counts(sfhe_ctx* c, uint64_t* hits, uint64_t* columns, uint64_t* fused, uint64_t* composed);
 /* Small polynomials (an encryption's v, e0, e1; the keys' errors and secret)
  * sampled on the device (sfp_sample_small) and on the host since the last
  * sfhe_op_stats reset (SFHE_DEV_SAMPLE=0, read per call, samples on the host;
@@ -255,6 +261,32 @@ int sfhe_sorter_place(sfhe_sorter* s, const sfhe_ct* rank, sfhe_ct* in, sfhe_ct*
  * depth needed. */
 int sfhe_sorter_sort_stable(sfhe_sorter* s, sfhe_ct* in, int n, int dg, int df, sfhe_ct** out);
 int sfhe_sorter_rank_stable(sfhe_sorter* s, const sfhe_ct* in, int n, int dg, int df, sfhe_ct** out);
+/* Engine extensions (additions at ABI 3): records -- several payload columns
+ * placed by ONE rank.  The placement's indicator depends on the rank alone,
+ * so it is evaluated once per batch for all columns; only the linear tail
+ * runs per column.  outs[i] holds exactly the residues of
+ * sfhe_sorter_place(rank, cols[i]).  Every column must be at one level and is
+ * left at the partition's slot count, as sfhe_sorter_place leaves its input.
+ * Payload values must lie in [-1, 1]: the placement error scales with |value|.
+ * count = 0, count > SFHE_MAX_COLUMNS or a NULL entry: SFHE_EINVAL (one
+ * column is allowed). */
+#define SFHE_MAX_COLUMNS 8
+int sfhe_sorter_place_many(sfhe_sorter* s, const sfhe_ct* rank, sfhe_ct* const* cols, size_t count,
+                           sfhe_ct** outs);
+/* rank (stable != 0: sfhe_sorter_rank_stable, else sfhe_sorter_rank) of the
+ * keys, then one placement of the keys and the `count` columns: *keys_out the
+ * sorted keys, outs[i] column i in the keys' order (stable: equal keys keep
+ * their input order).  count = 0 sorts the keys alone (cols / outs may be
+ * NULL).  stable = 1 needs mult_depth = sfhe_direct_sort_params' depth + 1;
+ * with less it returns SFHE_ESCHEME and the message names the depth needed.
+ * Captured like sfhe_sorter_sort, in a graph of its own: first call of a
+ * shape (levels, slots, column count, stable, sign configuration) eager,
+ * second captured, later ones replayed. */
+int sfhe_sorter_sort_records(sfhe_sorter* s, sfhe_ct* keys, sfhe_ct* const* cols, size_t count, int stable,
+                             int n, int dg, int df, sfhe_ct** keys_out, sfhe_ct** outs);
+/* nodes of the captured record sort (0 while none); sfhe_sorter_graph_nodes
+ * keeps reporting the plain / stable sort's graph */
+int sfhe_sorter_records_graph_nodes(const sfhe_sorter* s, uint64_t* nodes);
 /* Kernel / dependency nodes of the sorter's captured sort graph (engine
  * extension, no reference counterpart): sort() runs its first call of a shape
  * eagerly, captures the second into a hipGraph and replays it from then on

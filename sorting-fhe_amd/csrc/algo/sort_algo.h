@@ -18,6 +18,9 @@
 // apart), one level deeper.  Measured on the oracle, every
 // multiplicity up to all-equal at N = 256 passes the 0.01 output gate
 // (worst: 1.1e-3).  The reference-signature methods behave as before.
+// Records: placeMany places several columns by one rank with
+// the indicator evaluated once per batch, sortRecords = the (stable) rank of
+// a key column + placeMany of the keys and their payload columns.
 //
 // Engine-specific scheduling (identical slot values, fewer key switches):
 //   * baby-step rotations of one ciphertext share one hoisted ModUp;
@@ -632,6 +635,102 @@ class DirectSort : public SortBase<N> {
         return output;
     }
 
+    // blindRotationOptN of several columns' masked inputs [c][j]: the columns
+    // share the masks, so their giant-step sums are formed together
+    // (EvalMultAddPlainCols); each column's sums then rotate as there.
+    std::vector<Ciphertext<DCRTPoly>> blindRotationOptNCols(
+        const std::vector<std::vector<Ciphertext<DCRTPoly>>>& masked_inputs, int num_slots, int np, int ib,
+        int num_partition) {
+        std::vector<std::array<int, 5>> keys;
+        std::vector<int> steps;
+        for (int i = 0; i < (num_slots / N) / np; ++i) {
+            keys.push_back({1, 0, i, (int)masked_inputs[0][0]->GetLevel(), num_slots});
+            steps.push_back(i * np);
+        }
+        const auto masks = maskMemoMany(keys, np, [&](size_t i, int j) {
+            return m_cc->MakeCKKSPackedPlaintext(vectorRotate(generateMaskVectorN(num_slots, np * (int)i + j), j), 1,
+                                                 masked_inputs[0][j]->GetLevel(), nullptr, num_slots);
+        });
+        const auto giants = m_cc->EvalMultAddPlainCols(masked_inputs, masks);
+        std::vector<Ciphertext<DCRTPoly>> results;
+        for (const auto& g : giants) {
+            auto result = this->getZero()->Clone();
+            m_cc->EvalAddInPlace(result, rot.rotate(rot.rotateSum(g, steps), ib * num_partition));
+            results.push_back(result);
+        }
+        return results;
+    }
+
+    // The placement of several columns by ONE rank (records: a key and its
+    // payload columns).  The indicator `hit` depends on the
+    // rank alone: per batch z, the doubled-sinc PS and its level adjustment
+    // run once, exactly as in rotationIndexCheckN, and only the linear tail
+    // (hit (.) column, baby rotations, blind rotation, batch sum, folds) runs
+    // per column.  Column c of the result holds the residues of
+    // rotationIndexCheckN(ctx_Rank, cols[c]): the arithmetic is exact on
+    // canonical residues, so sharing `hit` changes none of them.  Every
+    // column is left at S slots, as rotationIndexCheckN leaves its input.
+    std::vector<Ciphertext<DCRTPoly>> placeMany(const Ciphertext<DCRTPoly>& ctx_Rank,
+                                                const std::vector<Ciphertext<DCRTPoly>>& cols) {
+        if (cols.empty()) throw OpenFHEException("placeMany: no columns");
+        for (const auto& c : cols)
+            if (c->GetLevel() != cols[0]->GetLevel())
+                throw OpenFHEException("placeMany: the columns must be at one level");
+        const sfhe::RankLayout L(N, max_batch);
+        sfhe::PhaseTimer ph(m_cc);
+        const size_t C = cols.size();
+        Plaintext idx = maskMemo({2, 0, 0, (int)ctx_Rank->GetLevel(), N}, [&](auto& v) {
+            v.push_back(m_cc->MakeCKKSPackedPlaintext(generateIndexVector(), 1, ctx_Rank->GetLevel(), nullptr, N));
+        })[0];
+        auto indexMinusRank = m_cc->EvalSub(idx, ctx_Rank);
+        indexMinusRank->SetSlots(L.S);
+        for (const auto& c : cols) c->SetSlots(L.S);  // (rotationIndexCheckN's side effect on its input)
+        const bool rebase = sfhe::sincRebase();
+        const auto& sincCoeffs = rebase ? sfhe::rebasedChebyshev(selectDoubledSincCoefficients<N>(), -1.0, 0.5)
+                                        : selectDoubledSincCoefficients<N>();
+        const double zmul = rebase ? 4.0 / 3.0 : 1.0, zadd = rebase ? 1.0 / 3.0 : 0.0;
+        std::vector<std::vector<Ciphertext<DCRTPoly>>> parts(C, std::vector<Ciphertext<DCRTPoly>>(L.B));
+        const sfhe::BatchSplit split(m_cc, L.B);
+        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
+        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());
+        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
+            const int b = split.mine[i];
+            Plaintext chk = maskMemo({3, b, 0, (int)indexMinusRank->GetLevel(), L.S}, [&](auto& v) {
+                v.push_back(m_cc->MakeCKKSPackedPlaintext(generateCheckingVectorN(L.S, b * L.P), 1,
+                                                          indexMinusRank->GetLevel(), nullptr, L.S));
+            })[0];
+            auto z = m_cc->EvalMult(m_cc->EvalSub(indexMinusRank, chk), zmul / N / 2);
+            if (rebase) z = m_cc->EvalAdd(z, zadd);
+            ph.mark("  place batch: z");
+            auto hit = m_cc->EvalChebyshevSeriesPS(z, sincCoeffs, -1, 1);
+            const uint32_t psLevel = z->GetLevel() + lbcrypto::ChebyshevPSDepth(
+                (uint32_t)selectDoubledSincCoefficients<N>().size() - 1);
+            if (hit->GetLevel() < psLevel) hit = m_cc->AdjustLevel(hit, psLevel);
+            ph.mark("  place batch: sinc PS (shared)");
+            std::vector<int> amounts(L.npPlace);
+            for (int k = 0; k < L.npPlace; ++k) amounts[k] = k;
+            std::vector<std::vector<Ciphertext<DCRTPoly>>> maskedRot(C);
+            for (size_t c = 0; c < C; ++c) maskedRot[c] = rot.rotateMany(m_cc->EvalMult(hit, cols[c]), amounts);
+            ph.mark("  place batch: masks + baby rotations");
+            auto placed = blindRotationOptNCols(maskedRot, L.S, L.npPlace, b, L.P);
+            for (size_t c = 0; c < C; ++c) parts[c][b] = placed[c];
+            ph.mark("  place batch: blind rotations");
+        });
+        m_cc->JoinLanes();
+        m_cc->NotePlacement(split.mine.size(), C);
+        std::vector<Ciphertext<DCRTPoly>> outputs(C);
+        for (size_t c = 0; c < C; ++c) {
+            split.gatherParts(m_cc, parts[c]);
+            auto output = this->getZero()->Clone();
+            for (int b = 0; b < L.B; ++b) m_cc->EvalAddInPlace(output, parts[c][b]);
+            for (int s = L.S / 2; s >= N; s /= 2) m_cc->EvalAddInPlace(output, rot.rotate(output, s));
+            output->SetSlots(N);
+            outputs[c] = output;
+        }
+        ph.mark("place: batch sums + folds");
+        return outputs;
+    }
+
     // ---- hybrid placement I (reference :815-891,
     // :1067-1229).  Rank as DirectSort; placement by an indicator matrix:
     // with M = min(N, 256) and num_slots = M*M per batch, slot (i, j) of
@@ -910,6 +1009,7 @@ class DirectSort : public SortBase<N> {
     ~DirectSort() override {
         m_plain.graph.reset();
         m_stable.graph.reset();
+        m_records.graph.reset();
         m_debugGraphs.reset();
     }
     // nodes of the captured sort of the last sort's mode (0: none yet / eager)
@@ -1094,6 +1194,124 @@ class DirectSort : public SortBase<N> {
         input_array->SetSlots(m_graph->in->GetSlots());  // sort()'s side effect on its input (:711)
         auto result = m_graph->out->Clone();
         result->SetSlots(m_graph->out->GetSlots());
+        return result;
+    }
+
+    // ---- records: a key column and its payload columns sorted by the key ----
+    // rank = the (stable) rank of the keys, then ONE placement of {keys,
+    // cols...} (placeMany): first the sorted keys, then the sorted columns.
+    // Payload values must lie in [-1, 1] like the keys: the placement's error
+    // scales with |value|.  stable = true needs sfhe::stableSortDepth levels
+    // (constructRankStable's check and message).  Graphs follow sortMode's
+    // protocol with a cache of their own: the first call of a shape runs
+    // eagerly, the second is captured over 1 + C sorter-owned input buffers,
+    // later ones copy the inputs in and replay.
+    struct RecordsKey {
+        GraphKey base;
+        bool stable = false;
+        std::vector<std::pair<uint32_t, uint32_t>> cols;  // each column's (level, slots)
+        bool operator==(const RecordsKey& o) const {
+            return base == o.base && stable == o.stable && cols == o.cols;
+        }
+    };
+    struct RecordsGraph {
+        std::shared_ptr<CryptoContextImpl<DCRTPoly>::CapturedGraph> g;
+        std::vector<Ciphertext<DCRTPoly>> in, out;  // keys first
+        RecordsKey key;
+    };
+    struct RecordsCache {
+        std::unique_ptr<RecordsGraph> graph;
+        RecordsKey warmKey;
+        bool warm = false;
+    };
+    RecordsCache m_records;
+
+    size_t recordsGraphNodes() const { return m_records.graph ? m_cc->GraphNodes(m_records.graph->g) : 0; }
+
+    std::vector<Ciphertext<DCRTPoly>> sortRecordsEager(const std::vector<Ciphertext<DCRTPoly>>& in,
+                                                       SignFunc SignFunc, SignConfig& Cfg, bool stable) {
+        auto ctx_Rank = stable ? constructRankStable(in[0], SignFunc, Cfg) : constructRank(in[0], SignFunc, Cfg);
+        return placeMany(ctx_Rank, in);
+    }
+
+    // {sorted keys, sorted cols...}
+    std::vector<Ciphertext<DCRTPoly>> sortRecords(const Ciphertext<DCRTPoly>& keys,
+                                                  const std::vector<Ciphertext<DCRTPoly>>& cols, SignFunc SignFunc,
+                                                  SignConfig& Cfg, bool stable) {
+        std::vector<Ciphertext<DCRTPoly>> in{keys};
+        in.insert(in.end(), cols.begin(), cols.end());
+        if (stable) {
+            const int need = (int)keys->GetLevel() + sfhe::stableSortDepth(N, Cfg.compos);
+            if ((int)m_cc->GetMultiplicativeDepth() < need)
+                throw OpenFHEException("stable record sort: needs multiplicative depth " + std::to_string(need) +
+                                       " (one level more than the plain sort for the tie term); the context has " +
+                                       std::to_string(m_cc->GetMultiplicativeDepth()));
+        }
+        const bool debug = dynamic_cast<const DebugEncryption*>(m_enc.get()) != nullptr;
+        if (m_graphOff || !graphsEnabled() || debug) return sortRecordsEager(in, SignFunc, Cfg, stable);
+        const sfhe::RankLayout L(N, max_batch);
+        RecordsKey key;
+        key.base.level = keys->GetLevel();
+        key.base.func = (int)SignFunc;
+        key.base.n = Cfg.compos.n;
+        key.base.dg = Cfg.compos.dg;
+        key.base.df = Cfg.compos.df;
+        key.base.multDepth = Cfg.multDepth;
+        key.stable = stable;
+        // (N and S slots select the same op sequence, as in sortMode)
+        auto slotsOf = [&](const Ciphertext<DCRTPoly>& c) {
+            return c->GetSlots() == (uint32_t)L.S ? (uint32_t)N : c->GetSlots();
+        };
+        key.base.slots = slotsOf(keys);
+        for (const auto& c : cols) key.cols.emplace_back(c->GetLevel(), slotsOf(c));
+        std::unique_ptr<RecordsGraph>& graph = m_records.graph;
+        if (!(graph && graph->key == key)) {
+            if (!(m_records.warm && m_records.warmKey == key)) {  // first call of this shape: eager, builds the masks
+                m_records.warm = true;
+                m_records.warmKey = key;
+                return sortRecordsEager(in, SignFunc, Cfg, stable);
+            }
+            graph.reset();
+            auto g = std::make_unique<RecordsGraph>();
+            g->key = key;
+            // sorter-owned input buffers in canonical form (see sortMode)
+            for (const auto& c : in) {
+                m_cc->Settle(c);
+                g->in.push_back(c->Clone());
+                m_cc->Settle(g->in.back());
+            }
+            if (!m_cc->BeginCapture()) {
+                m_graphOff = true;
+                return sortRecordsEager(in, SignFunc, Cfg, stable);
+            }
+            std::vector<Ciphertext<DCRTPoly>> out;
+            try {
+                out = sortRecordsEager(g->in, SignFunc, Cfg, stable);
+                // every output's final rows are written inside the region
+                for (auto& o : out) m_cc->Settle(o);
+            } catch (...) {
+                m_cc->EndCapture(nullptr);
+                m_graphOff = true;
+                throw;
+            }
+            g->g = m_cc->EndCapture(out.back());
+            if (!g->g) {
+                m_graphOff = true;
+                return sortRecordsEager(in, SignFunc, Cfg, stable);
+            }
+            g->out = out;
+            graph = std::move(g);
+        } else {
+            for (size_t c = 0; c < in.size(); ++c)
+                if (graph->in[c] != in[c]) m_cc->CopyCiphertextInto(graph->in[c], in[c]);
+        }
+        m_cc->Launch(graph->g);
+        std::vector<Ciphertext<DCRTPoly>> result;
+        for (size_t c = 0; c < in.size(); ++c) {
+            in[c]->SetSlots(graph->in[c]->GetSlots());  // placeMany's side effect on its inputs
+            result.push_back(graph->out[c]->Clone());
+            result.back()->SetSlots(graph->out[c]->GetSlots());
+        }
         return result;
     }
 

@@ -100,6 +100,9 @@ struct SorterBase {
     virtual Ct sortStable(const Ct& in, SignConfig& cfg) = 0;
     virtual Ct rankStable(const Ct& in, SignConfig& cfg) = 0;
     virtual Ct place(const Ct& rank, const Ct& in) = 0;
+    virtual std::vector<Ct> placeMany(const Ct& rank, const std::vector<Ct>& cols) = 0;
+    virtual std::vector<Ct> sortRecords(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, bool stable) = 0;
+    virtual size_t recordsGraphNodes() const = 0;
     virtual Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) = 0;
     virtual Ct hybrid(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk, int variant) = 0;
     virtual Ct place2N(const Ct& rank, const Ct& in) = 0;
@@ -134,6 +137,11 @@ struct Sorter : SorterBase {
         return ds.constructRankStable(in, SignFunc::CompositeSign, cfg);
     }
     Ct place(const Ct& r, const Ct& in) override { return ds.rotationIndexCheckN(r, in); }
+    std::vector<Ct> placeMany(const Ct& r, const std::vector<Ct>& cols) override { return ds.placeMany(r, cols); }
+    std::vector<Ct> sortRecords(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, bool stable) override {
+        return ds.sortRecords(keys, cols, SignFunc::CompositeSign, cfg, stable);
+    }
+    size_t recordsGraphNodes() const override { return ds.recordsGraphNodes(); }
     Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) override {
         return ds.sort_hybrid1(in, SignFunc::CompositeSign, cfg, sk);
     }
@@ -375,6 +383,16 @@ int sfhe_tie_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
     return SFHE_OK;
 }
 
+int sfhe_place_counts(sfhe_ctx* c, uint64_t* hits, uint64_t* columns, uint64_t* fused, uint64_t* composed) {
+    REQUIRE(c && hits && columns && fused && composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *hits = s.place_hits;
+    *columns = s.place_columns;
+    *fused = s.place_fused;
+    *composed = s.place_composed;
+    return SFHE_OK;
+}
+
 int sfhe_const_term_counts(sfhe_ctx* c, uint64_t* merged, uint64_t* single, uint64_t* composed) {
     REQUIRE(c && merged && single && composed, "null argument");
     auto s = c->cc->GetOpStats();
@@ -580,6 +598,34 @@ int sfhe_sorter_rank_stable(sfhe_sorter* s, const sfhe_ct* in, int n, int dg, in
 int sfhe_sorter_place(sfhe_sorter* s, const sfhe_ct* rank, sfhe_ct* in, sfhe_ct** out) {
     REQUIRE(s && rank && in && out, "null argument");
     return guard([&] { *out = wrap(s->impl->place(rank->ct, in->ct)); });
+}
+
+int sfhe_sorter_place_many(sfhe_sorter* s, const sfhe_ct* rank, sfhe_ct* const* cols, size_t count, sfhe_ct** outs) {
+    REQUIRE(s && rank && cols && outs, "null argument");
+    REQUIRE(count >= 1 && count <= SFHE_MAX_COLUMNS, "column count out of range (1 .. SFHE_MAX_COLUMNS)");
+    for (size_t i = 0; i < count; ++i) REQUIRE(cols[i], "null column");
+    return guard([&] {
+        std::vector<Ct> in;
+        for (size_t i = 0; i < count; ++i) in.push_back(cols[i]->ct);
+        auto placed = s->impl->placeMany(rank->ct, in);
+        for (size_t i = 0; i < count; ++i) outs[i] = wrap(placed[i]);
+    });
+}
+
+int sfhe_sorter_sort_records(sfhe_sorter* s, sfhe_ct* keys, sfhe_ct* const* cols, size_t count, int stable, int n,
+                             int dg, int df, sfhe_ct** keys_out, sfhe_ct** outs) {
+    REQUIRE(s && keys && keys_out && (count == 0 || (cols && outs)), "null argument");
+    REQUIRE(count <= SFHE_MAX_COLUMNS, "column count out of range (0 .. SFHE_MAX_COLUMNS)");
+    for (size_t i = 0; i < count; ++i) REQUIRE(cols[i], "null column");
+    return guard([&] {
+        Quiet q(s->ctx->quiet);
+        auto cfg = cfgOf(n, dg, df);
+        std::vector<Ct> in;
+        for (size_t i = 0; i < count; ++i) in.push_back(cols[i]->ct);
+        auto sorted = s->impl->sortRecords(keys->ct, in, cfg, stable != 0);
+        *keys_out = wrap(sorted[0]);
+        for (size_t i = 0; i < count; ++i) outs[i] = wrap(sorted[i + 1]);
+    });
 }
 
 int sfhe_sorter_sort_hybrid1(sfhe_sorter* s, sfhe_ct* in, int n, int dg, int df, sfhe_ct** out) {
@@ -844,6 +890,12 @@ int sfhe_sorter_graph_ntt_time(sfhe_sorter* s, int reps, double* ms, uint64_t* l
 int sfhe_sorter_graph_nodes(const sfhe_sorter* s, uint64_t* nodes) {
     REQUIRE(s && nodes, "null argument");
     *nodes = s->impl->graphNodes();
+    return SFHE_OK;
+}
+
+int sfhe_sorter_records_graph_nodes(const sfhe_sorter* s, uint64_t* nodes) {
+    REQUIRE(s && nodes, "null argument");
+    *nodes = s->impl->recordsGraphNodes();
     return SFHE_OK;
 }
 

@@ -3460,6 +3460,75 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMultAddPlain(
     return SfheInternal::traced(this, SfheInternal::rescale(this, t0, t1, level, slots), "EvalMultAddPlain");
 }
 
+// The column-aware macGroups: every column's sums are EvalMultAddPlain's
+// deferred products; where all of them are still deferred over one level and
+// one input count, and the backend has sfp_mac_plain2_cols, they are computed
+// now in their pending form by its tiles (the residues DeferredMacPlain::run
+// and macGroups store).  Otherwise they stay deferred and EvalRotateSum's
+// macGroups runs each column's groups.
+std::vector<std::vector<Ciphertext<DCRTPoly>>> CryptoContextImpl<DCRTPoly>::EvalMultAddPlainCols(
+    const std::vector<std::vector<Ciphertext<DCRTPoly>>>& a, const std::vector<const std::vector<Plaintext>*>& p) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    if (a.empty() || p.empty()) SFHE_THROW("operand count mismatch");
+    const size_t nc = a.size(), ng = p.size(), nin = a[0].size();
+    for (auto& col : a)
+        if (col.size() != nin) SFHE_THROW("operand count mismatch");
+    std::vector<std::vector<Ciphertext<DCRTPoly>>> out(nc);
+    for (size_t c = 0; c < nc; ++c)
+        for (size_t k = 0; k < ng; ++k) out[c].push_back(EvalMultAddPlain(a[c], *p[k]));
+    const char* knob = std::getenv("SFHE_PLACE_COLS");  // (read per call: tests switch it)
+    bool fuse = sfp_mac_plain2_cols && !(knob && *knob == '0') && nin <= SFP_MAC_MULTI_N && ng <= SFP_MAC_COLS_G &&
+                nc <= SFP_MAC_COLS_C;
+    std::vector<DeferredMacPlain*> macs;
+    for (size_t c = 0; c < nc && fuse; ++c)
+        for (size_t k = 0; k < ng && fuse; ++k) {
+            const auto& ct = *out[c][k];
+            auto* m = (ct.def && !ct.undo) ? dynamic_cast<DeferredMacPlain*>(ct.def.get()) : nullptr;
+            fuse = m && m->x0.size() == nin && m->level == out[0][0]->level - 1 &&
+                   (k == 0 || (m->x0 == macs[c * ng]->x0 && m->x1 == macs[c * ng]->x1));
+            macs.push_back(m);
+        }
+    if (fuse) {
+        const uint32_t level = macs[0]->level, ell = s->ellOf(level);
+        const size_t pw = s->polyWords(level);
+        std::vector<Plaintext> pts;
+        for (size_t k = 0; k < ng; ++k) pts.insert(pts.end(), p[k]->begin(), p[k]->end());
+        SfheInternal::encodeBatch(this, pts, level);
+        std::vector<const uint64_t*> mm, x0, x1;
+        for (auto& pt : pts) mm.push_back(SfheInternal::encoded(this, pt, level));
+        std::vector<DeviceBufferPtr> bufs;
+        std::vector<uint64_t*> o0, o1;
+        for (size_t c = 0; c < nc; ++c) {
+            x0.insert(x0.end(), macs[c * ng]->x0.begin(), macs[c * ng]->x0.end());
+            x1.insert(x1.end(), macs[c * ng]->x1.begin(), macs[c * ng]->x1.end());
+            for (auto& b : macs[c * ng]->pins) s->dep(b.get());
+            for (size_t k = 0; k < ng; ++k) {
+                bufs.push_back(s->alloc(2 * pw));
+                o0.push_back(bufs.back()->ptr);
+                o1.push_back(bufs.back()->ptr + pw);
+            }
+        }
+        fuse = sfp_mac_plain2_cols(s->dev, o0.data(), o1.data(), x0.data(), x1.data(), mm.data(), (uint32_t)nin,
+                                   (uint32_t)ng, (uint32_t)nc, s->qmap(ell)) == 0;
+        if (fuse) {
+            std::vector<std::shared_ptr<DeferredOp>> defs;  // (each keeps its pins alive until every sum is adopted)
+            for (size_t c = 0; c < nc; ++c)
+                for (size_t k = 0; k < ng; ++k) {
+                    defs.push_back(SfheInternal::takeDeferred(*out[c][k], true));
+                    SfheInternal::adoptPending(*out[c][k], bufs[c * ng + k], o0[c * ng + k], o1[c * ng + k]);
+                }
+        }
+    }
+    (fuse ? s->stats.place_fused : s->stats.place_composed) += nc * ng;
+    return out;
+}
+
+void CryptoContextImpl<DCRTPoly>::NotePlacement(uint64_t hits, uint64_t columns) {
+    st->stats.place_hits += hits;
+    st->stats.place_columns += columns;
+}
+
 // ============================================================================
 // rotations
 

@@ -422,6 +422,19 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     // level as summing the individually rescaled EvalMult(a_i, p_i)).
     Ciphertext<DCRTPoly> EvalMultAddPlain(const std::vector<Ciphertext<DCRTPoly>>& a,
                                           const std::vector<Plaintext>& p);
+    // Engine extension (records: several columns placed by one rank, DESIGN.md
+    // §4f): out[c][g] = EvalMultAddPlain(a[c], *p[g]) for columns a[c] of one
+    // length under the SAME plaintext sets.  Where the backend has prims.h
+    // sfp_mac_plain2_cols the sums are formed at once, pending (unrescaled, as
+    // EvalRotateSum takes them), by launches that read each plaintext once for
+    // a tile of columns; elsewhere (the C oracle, SFHE_PLACE_COLS=0 -- read per
+    // call --, operands of different levels, the prim declining) they stay
+    // deferred and each column takes today's path.  The same residues.
+    // OpStats place_fused / place_composed count the sums of each kind.
+    std::vector<std::vector<Ciphertext<DCRTPoly>>> EvalMultAddPlainCols(
+        const std::vector<std::vector<Ciphertext<DCRTPoly>>>& a, const std::vector<const std::vector<Plaintext>*>& p);
+    // a multi-column placement evaluated `hits` indicators for `columns` columns (OpStats)
+    void NotePlacement(uint64_t hits, uint64_t columns);
 
     // rotations
     Ciphertext<DCRTPoly> EvalRotate(const Ciphertext<DCRTPoly>& a, int32_t r);
@@ -661,6 +674,9 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         // constant terms c x (one-input weighted sums): inside a multi-term launch
         // (sfp_const_terms_rescale) / as one fused constant rescale / as a weighted sum, then a rescale
         uint64_t const_merged = 0, const_single = 0, const_composed = 0;
+        // multi-column placements: indicators evaluated, columns they served, giant-step sums formed
+        // by sfp_mac_plain2_cols / left to the per-column path
+        uint64_t place_hits = 0, place_columns = 0, place_fused = 0, place_composed = 0;
     };
     OpStats GetOpStats() const;
     void ResetOpStats();
@@ -743,7 +759,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 8
+#define SFHE_FACADE_ABI_VERSION 9
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

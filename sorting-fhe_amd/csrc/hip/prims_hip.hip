@@ -2445,6 +2445,119 @@ __global__ __launch_bounds__(kThreads) void k_mac_plain2_multi(const PtrListM L,
     }
 }
 
+// A tile of G giant-step sums for each of C columns (sfp_mac_plain2_cols): the
+// columns are different ciphertext sets a[c][j] / c[c][j] under the SAME
+// plaintexts b[g][j], so each plaintext word is read once for the tile's
+// columns and each ciphertext word once for its giants -- G + 2 C loads feed
+// 4 G C products.  Tiles hold G C <= 8 sums: the 32 FP64 accumulators of
+// k_mac_plain2_multi<8>.  The same exact residue sums as k_mac_plain2.
+constexpr int kMacColsTile = 8;     // sums per tile (G * C)
+constexpr int kMacColsMaxC = 4;     // widest tile
+struct PtrListC {
+    const u64* a[kMacColsMaxC * SFP_MAC_MULTI_N];  // [c * nin + j]
+    const u64* c[kMacColsMaxC * SFP_MAC_MULTI_N];
+    const u64* b[(kMacColsTile / 2) * SFP_MAC_MULTI_N];  // [g * nin + j] (G <= 4: a tile has C >= 2 or is sfp_mac_plain2_multi's)
+    u64* o0[kMacColsTile];  // [c * G + g]
+    u64* o1[kMacColsTile];
+};
+static_assert(sizeof(PtrListC) + 64 <= 4096, "k_mac_plain2_cols: the by-value pointer lists exceed the kernel-argument limit");
+template <int G, int C>
+__global__ __launch_bounds__(kThreads) void k_mac_plain2_cols(const PtrListC L, uint32_t nin, sfp_limbs m,
+                                                              const sf_barrett* __restrict__ bar, uint32_t logn,
+                                                              const double* __restrict__ qinvD) {
+    static_assert(G * C <= kMacColsTile && C <= kMacColsMaxC && 2 * G <= kMacColsTile, "tile shape");
+    const size_t pairs = ((size_t)m.count << logn) >> 1;
+    for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < pairs; i += (size_t)gridDim.x * kThreads) {
+        const size_t e = 2 * i;
+        const uint32_t prime = primeOf(m, (uint32_t)(e >> logn));
+        const sf_barrett B = loadBar(bar, prime);
+        if (B.q < kFpPrimeBound) {  // (uniform per wave)
+            const double qd = (double)B.q, qi = qinvD[prime];
+            double x0[C][G], y0[C][G], x1[C][G], y1[C][G];
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+#pragma unroll
+                for (int g = 0; g < G; ++g) x0[c][g] = y0[c][g] = x1[c][g] = y1[c][g] = 0.0;
+            for (uint32_t j = 0; j < nin; ++j) {
+                ulonglong2 a[C], cc[C], p[G];
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    a[c] = *reinterpret_cast<const ulonglong2*>(L.a[c * nin + j] + e);
+                    cc[c] = *reinterpret_cast<const ulonglong2*>(L.c[c * nin + j] + e);
+                }
+#pragma unroll
+                for (int g = 0; g < G; ++g) p[g] = *reinterpret_cast<const ulonglong2*>(L.b[g * nin + j] + e);
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const double px = u2d(p[g].x), py = u2d(p[g].y), pxq = px * qi, pyq = py * qi;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        x0[c][g] += fpMulMod(u2d(a[c].x), px, pxq, qd);
+                        y0[c][g] += fpMulMod(u2d(a[c].y), py, pyq, qd);
+                        x1[c][g] += fpMulMod(u2d(cc[c].x), px, pxq, qd);
+                        y1[c][g] += fpMulMod(u2d(cc[c].y), py, pyq, qd);
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    ulonglong2 o0, o1;
+                    o0.x = d2u(fpReduce(x0[c][g], qd, qi));
+                    o0.y = d2u(fpReduce(y0[c][g], qd, qi));
+                    o1.x = d2u(fpReduce(x1[c][g], qd, qi));
+                    o1.y = d2u(fpReduce(y1[c][g], qd, qi));
+                    *reinterpret_cast<ulonglong2*>(L.o0[c * G + g] + e) = o0;
+                    *reinterpret_cast<ulonglong2*>(L.o1[c * G + g] + e) = o1;
+                }
+        } else {  // (128-bit sums, at most four (giant, column) pairs at a time: the integer row's registers)
+            constexpr int GS = C >= 3 ? 1 : (4 / C < G ? 4 / C : G);
+#pragma unroll
+            for (int h = 0; h < G; h += GS) {
+                Acc x0[C][GS], y0[C][GS], x1[C][GS], y1[C][GS];
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+#pragma unroll
+                    for (int g = 0; g < GS; ++g) x0[c][g] = y0[c][g] = x1[c][g] = y1[c][g] = Acc{0, 0};
+                for (uint32_t j = 0; j < nin; ++j) {
+                    ulonglong2 a[C], cc[C];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        a[c] = *reinterpret_cast<const ulonglong2*>(L.a[c * nin + j] + e);
+                        cc[c] = *reinterpret_cast<const ulonglong2*>(L.c[c * nin + j] + e);
+                    }
+#pragma unroll
+                    for (int g = 0; g < GS; ++g) {
+                        if (h + g >= G) break;
+                        const ulonglong2 p = *reinterpret_cast<const ulonglong2*>(L.b[(h + g) * nin + j] + e);
+#pragma unroll
+                        for (int c = 0; c < C; ++c) {
+                            macc(x0[c][g], a[c].x, p.x);
+                            macc(y0[c][g], a[c].y, p.y);
+                            macc(x1[c][g], cc[c].x, p.x);
+                            macc(y1[c][g], cc[c].y, p.y);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+#pragma unroll
+                    for (int g = 0; g < GS; ++g) {
+                        if (h + g >= G) break;
+                        ulonglong2 o0, o1;
+                        o0.x = sf_reduce128_acc(x0[c][g].lo, x0[c][g].hi, &B);
+                        o0.y = sf_reduce128_acc(y0[c][g].lo, y0[c][g].hi, &B);
+                        o1.x = sf_reduce128_acc(x1[c][g].lo, x1[c][g].hi, &B);
+                        o1.y = sf_reduce128_acc(y1[c][g].lo, y1[c][g].hi, &B);
+                        *reinterpret_cast<ulonglong2*>(L.o0[c * G + h + g] + e) = o0;
+                        *reinterpret_cast<ulonglong2*>(L.o1[c * G + h + g] + e) = o1;
+                    }
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void k_mac_plain(u64* __restrict__ out, PtrList2 ab,
                                                         uint32_t nin, sfp_limbs m,
                                                         const sf_barrett* __restrict__ bar,
@@ -5481,6 +5594,66 @@ int sfp_mac_plain2_multi(sfp_dev* d, uint64_t* const* out0, uint64_t* const* out
         default: SFP_GO(k_mac_plain2_multi<8>, grid, dim3(kThreads), L, nin, m, d->bar, d->logn, d->qinvD); break;
     }
     checkLaunch(d, "mac_plain2_multi");
+    return 0;
+}
+
+template <int G, int C>
+static void goMacCols(sfp_dev* d, const PtrListC& L, uint32_t nin, sfp_limbs m) {
+    const dim3 grid(ewGrid(((size_t)m.count * d->n) / 2));
+    SFP_GO((k_mac_plain2_cols<G, C>), grid, dim3(kThreads), L, nin, m, d->bar, d->logn, d->qinvD);
+}
+
+int sfp_mac_plain2_cols(sfp_dev* d, uint64_t* const* out0, uint64_t* const* out1, const uint64_t* const* a0,
+                        const uint64_t* const* a1, const uint64_t* const* b, uint32_t nin, uint32_t ng, uint32_t nc,
+                        sfp_limbs m) {
+    if (!ng || !nc || !nin || nin > SFP_MAC_MULTI_N || ng > SFP_MAC_COLS_G || nc > SFP_MAC_COLS_C || d->n < 2)
+        return -1;
+    uintptr_t bits = 0;  // 16-byte accesses need aligned rows
+    for (uint32_t k = 0; k < nc * ng; ++k) bits |= (uintptr_t)out0[k] | (uintptr_t)out1[k];
+    for (uint32_t k = 0; k < nc * nin; ++k) bits |= (uintptr_t)a0[k] | (uintptr_t)a1[k];
+    for (uint32_t k = 0; k < ng * nin; ++k) bits |= (uintptr_t)b[k];
+    if (bits & 15) return -1;
+    if (!m.count) return 0;
+    if (!limbsOk(d, m, "mac_plain2_cols")) return 0;
+    // the (giants x columns) tile: 4 x 2 reads 8 words per 8 sums and term, 2 x 4
+    // reads 10 (as k_mac_plain2_multi<8>); SFHE_PLACE_TILE=2x4 selects the latter (A/B)
+    const char* tv = std::getenv("SFHE_PLACE_TILE");
+    const bool wide = tv && tv[0] == '2';
+    const uint32_t TG = wide ? 2 : 4, TC = wide ? 4 : 2;
+    for (uint32_t c0 = 0; c0 < nc; c0 += TC)
+        for (uint32_t g0 = 0; g0 < ng; g0 += TG) {
+            const uint32_t C = std::min(TC, nc - c0), G = std::min(TG, ng - g0);
+            PtrListC L;
+            std::memset(&L, 0, sizeof L);
+            for (uint32_t c = 0; c < C; ++c) {
+                for (uint32_t j = 0; j < nin; ++j) {
+                    L.a[c * nin + j] = a0[(size_t)(c0 + c) * nin + j];
+                    L.c[c * nin + j] = a1[(size_t)(c0 + c) * nin + j];
+                }
+                for (uint32_t g = 0; g < G; ++g) {
+                    L.o0[c * G + g] = out0[(size_t)(c0 + c) * ng + g0 + g];
+                    L.o1[c * G + g] = out1[(size_t)(c0 + c) * ng + g0 + g];
+                }
+            }
+            for (uint32_t g = 0; g < G; ++g)
+                for (uint32_t j = 0; j < nin; ++j) L.b[g * nin + j] = b[(size_t)(g0 + g) * nin + j];
+            // (each specialisation launched by name: see tests/test_kernel_symbols.py)
+            switch (G * 8 + C) {
+                case 1 * 8 + 1: goMacCols<1, 1>(d, L, nin, m); break;
+                case 2 * 8 + 1: goMacCols<2, 1>(d, L, nin, m); break;
+                case 3 * 8 + 1: goMacCols<3, 1>(d, L, nin, m); break;
+                case 4 * 8 + 1: goMacCols<4, 1>(d, L, nin, m); break;
+                case 1 * 8 + 2: goMacCols<1, 2>(d, L, nin, m); break;
+                case 2 * 8 + 2: goMacCols<2, 2>(d, L, nin, m); break;
+                case 3 * 8 + 2: goMacCols<3, 2>(d, L, nin, m); break;
+                case 4 * 8 + 2: goMacCols<4, 2>(d, L, nin, m); break;
+                case 1 * 8 + 3: goMacCols<1, 3>(d, L, nin, m); break;
+                case 2 * 8 + 3: goMacCols<2, 3>(d, L, nin, m); break;
+                case 1 * 8 + 4: goMacCols<1, 4>(d, L, nin, m); break;
+                default: goMacCols<2, 4>(d, L, nin, m); break;
+            }
+        }
+    checkLaunch(d, "mac_plain2_cols");
     return 0;
 }
 

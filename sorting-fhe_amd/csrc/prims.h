@@ -376,6 +376,25 @@ SFP_OPTIONAL int sfp_const_terms_rescale(sfp_dev* d, const uint64_t* in, size_t 
 SFP_OPTIONAL int sfp_tie_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const uint64_t* s0,
                                 const uint64_t* s1, const uint64_t* w, const uint64_t* k, sfp_limbs m);
 
+// ---- optional: the giant-step sums of several columns under one plaintext set ----
+// nc columns (records' payloads placed by one rank) share the ng x nin
+// plaintexts b[g * nin + j] of sfp_mac_plain2_multi; column c has its own
+// ciphertext rows a0[c * nin + j] / a1[c * nin + j]:
+//   out0[c * ng + g] = sum_j a0[c * nin + j] * b[g * nin + j],  out1 likewise with a1
+// (ng <= SFP_MAC_COLS_G, nc <= SFP_MAC_COLS_C, nin <= SFP_MAC_MULTI_N; all
+// host arrays of device pointers to 16-byte aligned rows).  Issued as tiles of
+// giants x columns: each plaintext word is read once for a tile's columns and
+// each ciphertext word once for its giants.  The canonical residues of nc
+// sfp_mac_plain2_multi calls (nc * ng sfp_mac_plain2 calls).  No upload and no
+// host synchronisation: capturable, any lane.  Weak like the prims above:
+// where its address is null (the C oracle) or it returns -1 (a shape it does
+// not handle: nothing done), the host layer runs sfp_mac_plain2_multi per column.
+#define SFP_MAC_COLS_G 64
+#define SFP_MAC_COLS_C 16
+SFP_OPTIONAL int sfp_mac_plain2_cols(sfp_dev* d, uint64_t* const* out0, uint64_t* const* out1,
+                                     const uint64_t* const* a0, const uint64_t* const* a1, const uint64_t* const* b,
+                                     uint32_t nin, uint32_t ng, uint32_t nc, sfp_limbs m);
+
 // ---- optional: CKKS decoding on the device (the end of a decryption) ----------
 // `count` row sets src + b * srcStride, each nl (1 or 2) COEFFICIENT-domain
 // rows of n words modulo primes 0 .. nl-1 (c0 + c1 s after its inverse NTT),

@@ -50,7 +50,10 @@ ABI_SYMBOLS = [
     "sfhe_encrypt_batch", "sfhe_sample_counts",
     "sfhe_sorter_sort_stable", "sfhe_sorter_rank_stable", "sfhe_tie_counts",
     "sfhe_const_term_counts",
+    "sfhe_sorter_place_many", "sfhe_sorter_sort_records", "sfhe_sorter_records_graph_nodes", "sfhe_place_counts",
 ]
+
+MAX_COLUMNS = 8  # SFHE_MAX_COLUMNS
 
 
 class SfheError(RuntimeError):
@@ -176,6 +179,11 @@ _SIGS = {
     "sfhe_sorter_sort_stable": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _PVP]),
     "sfhe_sorter_rank_stable": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _PVP]),
     "sfhe_tie_counts": (C.c_int, [_VP, _PU64, _PU64]),
+    "sfhe_sorter_place_many": (C.c_int, [_VP, _VP, _PVP, C.c_size_t, _PVP]),
+    "sfhe_sorter_sort_records": (C.c_int, [_VP, _VP, _PVP, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _PVP,
+                                           _PVP]),
+    "sfhe_sorter_records_graph_nodes": (C.c_int, [_VP, _PU64]),
+    "sfhe_place_counts": (C.c_int, [_VP, _PU64, _PU64, _PU64, _PU64]),
     "sfhe_const_term_counts": (C.c_int, [_VP, _PU64, _PU64, _PU64]),
 }
 
@@ -491,6 +499,14 @@ class Engine:
         self._chk(self.lib.sfhe_tie_counts(self.ctx, C.byref(f), C.byref(c)))
         return f.value, c.value
 
+    def place_counts(self):
+        """(hits, columns, fused, composed) of multi-column placements since the last op_stats
+        reset: indicators evaluated, columns they served, giant-step sums formed by
+        sfp_mac_plain2_cols and by the per-column path."""
+        v = [C.c_uint64() for _ in range(4)]
+        self._chk(self.lib.sfhe_place_counts(self.ctx, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def const_term_counts(self):
         """(merged, single, composed) constant terms c*x since the last op_stats reset: inside a
         multi-term launch, as one fused constant rescale, as a weighted sum then a rescale."""
@@ -648,6 +664,31 @@ class Sorter:
 
     def place(self, rank: Ct, ct: Ct) -> Ct:
         return self.eng._new(self.eng.lib.sfhe_sorter_place, self.h, rank.h, ct.h)
+
+    def place_many(self, rank: Ct, cts) -> list:
+        """place(rank, ct) of every column with ONE indicator evaluation per batch: the same
+        residues as the separate calls.  Payload values must lie in [-1, 1]."""
+        cts = list(cts)
+        hs = (_VP * max(len(cts), 1))(*[c.h if c is not None else None for c in cts])
+        outs = (_VP * max(len(cts), 1))()
+        self.eng._chk(self.eng.lib.sfhe_sorter_place_many(self.h, rank.h, hs, len(cts), outs))
+        return [Ct(self.eng, C.c_void_p(outs[k])) for k in range(len(cts))]
+
+    def sort_records(self, keys: Ct, cts=(), stable: bool = True, n: int = 3, dg: int = 2, df: int = 2):
+        """(sorted keys, [columns in the keys' order]); stable: equal keys keep their input
+        order and the context needs direct_sort_params' depth + 1 (SfheError otherwise)."""
+        cts = list(cts)
+        hs = (_VP * max(len(cts), 1))(*[c.h if c is not None else None for c in cts])
+        outs = (_VP * max(len(cts), 1))()
+        k = C.c_void_p()
+        self.eng._chk(self.eng.lib.sfhe_sorter_sort_records(self.h, keys.h, hs, len(cts), int(bool(stable)), n, dg,
+                                                            df, C.byref(k), outs))
+        return Ct(self.eng, k), [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cts))]
+
+    def records_graph_nodes(self) -> int:
+        v = C.c_uint64()
+        self.eng._chk(self.eng.lib.sfhe_sorter_records_graph_nodes(self.h, C.byref(v)))
+        return v.value
 
     def sort_hybrid1(self, ct: Ct, n: int = 3, dg: int = 2, df: int = 2) -> Ct:
         """DirectSort<N>::sort_hybrid1 (reference sort_algo.h:1213-1229)."""
