@@ -1997,7 +1997,10 @@ CryptoContextImpl<DCRTPoly>::CryptoContextImpl(const CCParams<CryptoContextCKKSR
     }
     const uint32_t sbits = p.GetScalingModSize();
     const uint32_t fbits = p.GetFirstModSize();
-    if (sbits < 20 || sbits > 60) SFHE_THROW("scaling mod size must be in [20, 60]");
+    // (modarith.h: below SF_MIN_PRIME_BITS a full word is outside sf_reduce128's range)
+    if (sbits < SF_MIN_PRIME_BITS || sbits > SF_MAX_PRIME_BITS)
+        SFHE_THROW("scaling mod size must be in [" + std::to_string(SF_MIN_PRIME_BITS) + ", " +
+                   std::to_string(SF_MAX_PRIME_BITS) + "]");
     if (fbits < sbits || fbits > 60) SFHE_THROW("first mod size must be in [scale bits, 60]");
     s.dnum = p.GetNumLargeDigits();
     if (s.dnum == 0 && std::getenv("SFHE_DNUM")) s.dnum = (uint32_t)std::atoi(std::getenv("SFHE_DNUM"));  // (A/B)

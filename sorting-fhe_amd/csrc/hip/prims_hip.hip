@@ -4678,6 +4678,13 @@ sfp_dev* sfp_create(int device, const sfp_tables* t) {
         // pass stages 2^logR - 1 <= kNttColTw twiddles in LDS (logR <= 9)
         return nullptr;
     }
+    for (uint32_t i = 0; i < d->np; ++i)  // (modarith.h: the reductions' range)
+        if (t->primes[i] >> (SF_MIN_PRIME_BITS - 1) == 0 || t->primes[i] >> SF_MAX_PRIME_BITS) {
+            std::fprintf(stderr, "sfhe: prime %u (%llu) is outside the supported %d..%d bits\n", i,
+                         (unsigned long long)t->primes[i], SF_MIN_PRIME_BITS, SF_MAX_PRIME_BITS);
+            delete d;
+            return nullptr;
+        }
     d->nLanes = 4;
     if (const char* v = std::getenv("SFHE_LANES"))
         d->nLanes = std::max(1, std::min(SFP_MAX_LANES - SFP_BATCH_MAX, std::atoi(v)));

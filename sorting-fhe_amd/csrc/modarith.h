@@ -63,6 +63,13 @@ typedef struct {
 // for the widest lazy sum of products).  The loop is capped: operands that
 // break the precondition (non-canonical residues) give a wrong result in
 // bounded time instead of ~2^24 iterations per word on the GPU.
+// Supported primes: sf_reduce128_acc and the callers that reduce one full
+// word (a signed coefficient, a residue of another prime: sf_reduce128(a, 0))
+// hand in values up to 2^64 + 2^(2b), so the 64 steps suffice only where
+// 2 + 2^64 / 2^(2b) + 1 <= 64: primes of SF_MIN_PRIME_BITS bits or more.  The
+// context and the HIP sfp_create refuse smaller primes.
+#define SF_MIN_PRIME_BITS 30
+#define SF_MAX_PRIME_BITS 60
 SF_HD u64 sf_reduce128(u64 zlo, u64 zhi, const sf_barrett* m) {
     const uint32_t b = m->b;
     // x = z >> (b-1)
@@ -78,6 +85,7 @@ SF_HD u64 sf_reduce128(u64 zlo, u64 zhi, const sf_barrett* m) {
 
 // Reduce any 128-bit value (e.g. a lazily accumulated sum of products):
 // reduce the high word mod q, fold it with 2^64 mod q, then Barrett.
+// Both steps hand sf_reduce128 a value up to 2^64 + 2^(2b) (see its range).
 SF_HD u64 sf_reduce128_acc(u64 zlo, u64 zhi, const sf_barrett* m) {
     u64 h = sf_reduce128(zhi, 0, m);
     u64 tlo = h * m->r64;
