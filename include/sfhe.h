@@ -31,7 +31,9 @@ extern "C" {
  * sfhe_encrypt_batch and sfhe_sample_counts, and sfhe_sorter_sort_stable,
  * sfhe_sorter_rank_stable and sfhe_tie_counts, and sfhe_const_term_counts, and
  * the record sort: SFHE_MAX_COLUMNS, sfhe_sorter_place_many,
- * sfhe_sorter_sort_records, sfhe_sorter_records_graph_nodes, sfhe_place_counts) */
+ * sfhe_sorter_sort_records, sfhe_sorter_records_graph_nodes, sfhe_place_counts,
+ * and the selection: sfhe_select_params, sfhe_sorter_select_ranked,
+ * sfhe_sorter_select, sfhe_eval_rotate_fold, sfhe_select_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -122,6 +124,10 @@ int sfhe_const_term_counts(sfhe_ctx* c, uint64_t* merged, uint64_t* single, uint
  * served, giant-step sums issued through sfp_mac_plain2_cols, and through the per-column path
  * (SFHE_PLACE_COLS=0, read per call, takes the per-column path; the results are bit-identical) */
 int sfhe_place_counts(sfhe_ctx* c, uint64_t* hits, uint64_t* columns, uint64_t* fused, uint64_t* composed);
+/* Since the last sfhe_op_stats reset: indicator batches the selections ran, and
+ * sfhe_eval_rotate_fold calls (the selections' included) whose inner products
+ * were one launch / were composed of the generic primitives. */
+int sfhe_select_counts(sfhe_ctx* c, uint64_t* batches, uint64_t* fold_fused, uint64_t* fold_composed);
 /* Small polynomials (an encryption's v, e0, e1; the keys' errors and secret)
  * sampled on the device (sfp_sample_small) and on the host since the last
  * sfhe_op_stats reset (SFHE_DEV_SAMPLE=0, read per call, samples on the host;
@@ -206,6 +212,15 @@ int sfhe_eval_rotate(sfhe_ctx* c, const sfhe_ct* a, int32_t r, sfhe_ct** out);
  * output aggregation of the giant steps of vecRotsOpt / blindRotationOptN,
  * src/sort_algo.h:342-364, 561-584, which sum individually rotated terms) */
 int sfhe_eval_rotate_sum(sfhe_ctx* c, const sfhe_ct* const* a, const int32_t* r, size_t count, sfhe_ct** out);
+/* sum_{k < count} EvalRotate(a, k * stride), 2 <= count <= 8 (engine extension,
+ * no reference counterpart): the rotations of ONE ciphertext share its ModUp
+ * and one ModDown, and on the device their key inner products are one launch
+ * (SFHE_SELECT_FOLD=0, read per call: one permutation and one accumulating
+ * inner product per term -- the same residues).  Term 0 is `a` itself; a term
+ * whose amount is a multiple of a's slot count is added as it is; any other
+ * amount needs its rotation key (SFHE_ESCHEME; the message names the amount).
+ * count outside [2, 8]: SFHE_EINVAL. */
+int sfhe_eval_rotate_fold(sfhe_ctx* c, const sfhe_ct* a, int32_t stride, uint32_t count, sfhe_ct** out);
 /* CKKS bootstrapping (OpenFHE's EvalBootstrapSetup + EvalBootstrapKeyGen and
  * EvalBootstrap, as src/k-way/EvalUtils.cpp:57-86 and src/sort_algo.h:1437
  * call them): setup for ciphertexts of `slots` slots with the level budget
@@ -284,6 +299,29 @@ int sfhe_sorter_place_many(sfhe_sorter* s, const sfhe_ct* rank, sfhe_ct* const* 
  * second captured, later ones replayed. */
 int sfhe_sorter_sort_records(sfhe_sorter* s, sfhe_ct* keys, sfhe_ct* const* cols, size_t count, int stable,
                              int n, int dg, int df, sfhe_ct** keys_out, sfhe_ct** outs);
+/* Engine extensions (additions at ABI 3): selection by rank -- order
+ * statistics (minimum, maximum, median, quantiles, the k smallest) without
+ * the full placement.  `targets` holds `count` distinct ranks in [0, N), 1 <=
+ * count <= N; *out is an N-slot ciphertext whose slot i < count holds the
+ * element of rank targets[i] (0 = the smallest) and whose other slots hold 0
+ * up to noise, at the level sfhe_sorter_place leaves.  The indicator runs
+ * ceil(count / Psel) batches, Psel = min(nextpow2(count), P), instead of the
+ * placement's N / P.  Duplicate targets, a target >= N, count = 0 or count >
+ * N: SFHE_EINVAL.  A missing rotation key of the in-partition folds or too
+ * little depth: SFHE_ESCHEME, and the message names the amount or the depth.
+ * Always eager (never captured).
+ * sfhe_select_params: sfhe_direct_sort_params' depth and its rotation list
+ * united with the folds' amounts {s, 2s, 3s : s = 4^i < N} (sorted, no
+ * repeats); create the sorter with that list (sfhe_sorter_create_rot).
+ * sfhe_sorter_select_ranked selects `in` by a rank computed before
+ * (sfhe_sorter_rank / _rank_stable of `in` or of a key column: records);
+ * sfhe_sorter_select computes the rank of `in` first (stable != 0: the stable
+ * rank, which needs depth + 1 and selects correctly among duplicate values). */
+int sfhe_select_params(uint32_t N, uint32_t* mult_depth, int32_t* rotations, size_t cap, size_t* count);
+int sfhe_sorter_select_ranked(sfhe_sorter* s, const sfhe_ct* rank, const sfhe_ct* in, const uint32_t* targets,
+                              size_t count, sfhe_ct** out);
+int sfhe_sorter_select(sfhe_sorter* s, const sfhe_ct* in, const uint32_t* targets, size_t count, int stable, int n,
+                       int dg, int df, sfhe_ct** out);
 /* nodes of the captured record sort (0 while none); sfhe_sorter_graph_nodes
  * keeps reporting the plain / stable sort's graph */
 int sfhe_sorter_records_graph_nodes(const sfhe_sorter* s, uint64_t* nodes);

@@ -731,6 +731,151 @@ class DirectSort : public SortBase<N> {
         return outputs;
     }
 
+    // ---- selection by rank: order statistics without the
+    // full placement.  rotationIndexCheckN is offset-major -- slot pN + r of
+    // batch b asks "does element r move left by bP + p?" -- so every one of
+    // its B = N/P batches (a doubled-sinc PS each) feeds every output.  Here
+    // the layout is target-major: partition p of batch b asks "which element
+    // has rank t = targets[b Psel + p]?", K targets take ceil(K / Psel)
+    // batches, Psel = min(nextpow2(K), P) partitions of N slots:
+    //   hit[pN + r] = D(((t - rank_r) zmul/2N) + zadd), t - rank_r in (-N, N):
+    //                 only the hit at 0 can occur (the same rebased doubled
+    //                 sinc, PS and level adjustment as the placement);
+    //   masked = hit (.) input; its N slots of a partition are summed into
+    //   slot pN by radix-4 EvalRotateFold steps (strides 1, 4, 16, ..., a
+    //   last step of 2 terms where log2 N is odd);
+    //   one plaintext mask keeps slot pN of the real targets -- the level
+    //   `place` spends on its masks -- inside the baby/giant-step move of that
+    //   slot to a slot congruent to c = b Psel + p modulo N: a left rotation
+    //   by N - c = base_b + p', p' = Psel - 1 - p = np i + j, base_b =
+    //   N + 1 - (b + 1) Psel (baby steps j, giant steps np i, then base_b);
+    //   the batches are summed and the folds S/2 .. N make the sum N-periodic.
+    // Slot i < K of the result holds the element of rank targets[i], the
+    // other slots 0 up to noise; the level is the one `place` leaves.  Runs
+    // eagerly (no graph).  The masks depend on the target list, which is
+    // part of their memo key (an id per distinct list, kept for the sorter's
+    // lifetime: a caller cycling through many lists grows the memo).
+    std::map<std::vector<int>, int> m_targetIds;
+    int targetListId(const std::vector<int>& targets) {
+        std::lock_guard<std::mutex> g(m_masksMu);
+        auto it = m_targetIds.find(targets);
+        if (it != m_targetIds.end()) return it->second;
+        const int id = (int)m_targetIds.size();
+        return m_targetIds[targets] = id;
+    }
+
+    // sum of the N slots of every partition into its first slot
+    Ciphertext<DCRTPoly> foldPartitions(Ciphertext<DCRTPoly> x) {
+        int stride = 1;
+        for (; stride * 4 <= N; stride *= 4) x = m_cc->EvalRotateFold(x, stride, 4);
+        if (stride < N) x = m_cc->EvalRotateFold(x, stride, 2);
+        return x;
+    }
+
+    Ciphertext<DCRTPoly> selectRanks(const Ciphertext<DCRTPoly>& ctx_Rank, const Ciphertext<DCRTPoly>& input_array,
+                                     const std::vector<int>& targets) {
+        const int K = (int)targets.size();
+        if (K < 1 || K > N) throw std::invalid_argument("select: the target count must be in [1, N]");
+        {
+            std::vector<char> seen(N, 0);
+            for (int t : targets) {
+                if (t < 0 || t >= N) throw std::invalid_argument("select: target rank " + std::to_string(t) +
+                                                                 " is outside [0, N)");
+                if (seen[t]) throw std::invalid_argument("select: duplicate target rank " + std::to_string(t));
+                seen[t] = 1;
+            }
+        }
+        const int ps = (int)lbcrypto::ChebyshevPSDepth((uint32_t)selectDoubledSincCoefficients<N>().size() - 1);
+        const int need = (int)ctx_Rank->GetLevel() + 1 + ps + 1 + 1;
+        if ((int)m_cc->GetMultiplicativeDepth() < need)
+            throw OpenFHEException("select: needs multiplicative depth " + std::to_string(need) +
+                                   " from a rank at level " + std::to_string(ctx_Rank->GetLevel()) +
+                                   "; the context has " + std::to_string(m_cc->GetMultiplicativeDepth()));
+        const sfhe::RankLayout L(N, max_batch);
+        sfhe::PhaseTimer ph(m_cc);
+        int Psel = 1;
+        while (Psel < K && Psel < L.P) Psel *= 2;
+        const int S = N * Psel, Bsel = (K + Psel - 1) / Psel;
+        const int np = 1 << (sfhe::ilog2(Psel) / 2);
+        const int tid = targetListId(targets);
+        auto rankS = ctx_Rank->Clone();
+        rankS->SetSlots(S);
+        auto input = input_array->Clone();
+        input->SetSlots(S);
+        const bool rebase = sfhe::sincRebase();
+        const auto& sincCoeffs = rebase ? sfhe::rebasedChebyshev(selectDoubledSincCoefficients<N>(), -1.0, 0.5)
+                                        : selectDoubledSincCoefficients<N>();
+        const double zmul = rebase ? 4.0 / 3.0 : 1.0, zadd = rebase ? 1.0 / 3.0 : 0.0;
+        std::vector<Ciphertext<DCRTPoly>> parts(Bsel);
+        const sfhe::BatchSplit split(m_cc, Bsel);
+        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
+        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());
+        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
+            const int b = split.mine[i];
+            // T[pN + r] = targets[b Psel + p] (a padded partition repeats the batch's first target)
+            Plaintext tgt = maskMemo({13, b, tid, (int)rankS->GetLevel(), S}, [&](auto& v) {
+                std::vector<double> T(S);
+                for (int p = 0; p < Psel; ++p) {
+                    const int k = b * Psel + p;
+                    std::fill(T.begin() + (size_t)p * N, T.begin() + (size_t)(p + 1) * N,
+                              (double)targets[k < K ? k : b * Psel]);
+                }
+                v.push_back(m_cc->MakeCKKSPackedPlaintext(T, 1, rankS->GetLevel(), nullptr, S));
+            })[0];
+            // (t - rank_r) / 2N  in (-1/2, 1/2)
+            auto z = m_cc->EvalMult(m_cc->EvalSub(tgt, rankS), zmul / N / 2);
+            if (rebase) z = m_cc->EvalAdd(z, zadd);
+            ph.mark("  select batch: z");
+            auto hit = m_cc->EvalChebyshevSeriesPS(z, sincCoeffs, -1, 1);
+            const uint32_t psLevel = z->GetLevel() + (uint32_t)ps;
+            if (hit->GetLevel() < psLevel) hit = m_cc->AdjustLevel(hit, psLevel);
+            ph.mark("  select batch: sinc PS");
+            auto summed = foldPartitions(m_cc->EvalMult(hit, input));
+            ph.mark("  select batch: mask + in-partition folds");
+            // the move: baby steps j, giant steps np i, then base_b
+            std::vector<int> amounts(np);
+            for (int j = 0; j < np; ++j) amounts[j] = j;
+            auto pre = rot.rotateMany(summed, amounts);
+            std::vector<std::array<int, 5>> keys;
+            std::vector<int> steps;
+            for (int g = 0; g < Psel / np; ++g) {
+                keys.push_back({14, tid, b * 1024 + g, (int)pre[0]->GetLevel(), S});
+                steps.push_back(g * np);
+            }
+            const auto masks = maskMemoMany(keys, np, [&](size_t g, int j) {
+                std::vector<double> m(S, 0.0);
+                const int p = Psel - 1 - (np * (int)g + j);
+                if (b * Psel + p < K) m[(size_t)p * N] = 1.0;
+                return m_cc->MakeCKKSPackedPlaintext(vectorRotate(m, j), 1, pre[j]->GetLevel(), nullptr, S);
+            });
+            std::vector<Ciphertext<DCRTPoly>> giants;
+            for (const auto* m : masks) {
+                giants.push_back(m_cc->EvalMultAddPlain(pre, *m));
+                giants.back()->SetSlots(S);
+            }
+            const int base = (N + 1 - (b + 1) * Psel) % S;
+            parts[b] = rot.rotate(rot.rotateSum(giants, steps), base);
+            ph.mark("  select batch: move");
+        });
+        m_cc->JoinLanes();
+        m_cc->NoteSelection(split.mine.size());
+        split.gatherParts(m_cc, parts);
+        auto output = this->getZero()->Clone();
+        output->SetSlots(S);
+        for (int b = 0; b < Bsel; ++b) m_cc->EvalAddInPlace(output, parts[b]);
+        for (int s = S / 2; s >= N; s /= 2) m_cc->EvalAddInPlace(output, rot.rotate(output, s));
+        ph.mark("select: batch sum + folds");
+        output->SetSlots(N);
+        return output;
+    }
+
+    // The (stable) rank of `input_array`, then selectRanks of its own values.
+    Ciphertext<DCRTPoly> select(const Ciphertext<DCRTPoly>& input_array, const std::vector<int>& targets,
+                                SignFunc SignFunc, SignConfig& Cfg, bool stable) {
+        auto rank = stable ? constructRankStable(input_array, SignFunc, Cfg) : constructRank(input_array, SignFunc, Cfg);
+        return selectRanks(rank, input_array, targets);
+    }
+
     // ---- hybrid placement I (reference :815-891,
     // :1067-1229).  Rank as DirectSort; placement by an indicator matrix:
     // with M = min(N, 256) and num_slots = M*M per batch, slot (i, j) of

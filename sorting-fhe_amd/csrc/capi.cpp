@@ -95,6 +95,7 @@ SignConfig cfgOf(int n, int dg, int df) { return SignConfig(CompositeSignConfig(
 
 struct SorterBase {
     virtual ~SorterBase() = default;
+    virtual uint32_t size() const = 0;
     virtual Ct sort(const Ct& in, SignConfig& cfg) = 0;
     virtual Ct rank(const Ct& in, SignConfig& cfg) = 0;
     virtual Ct sortStable(const Ct& in, SignConfig& cfg) = 0;
@@ -103,6 +104,8 @@ struct SorterBase {
     virtual std::vector<Ct> placeMany(const Ct& rank, const std::vector<Ct>& cols) = 0;
     virtual std::vector<Ct> sortRecords(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, bool stable) = 0;
     virtual size_t recordsGraphNodes() const = 0;
+    virtual Ct selectRanks(const Ct& rank, const Ct& in, const std::vector<int>& targets) = 0;
+    virtual Ct select(const Ct& in, const std::vector<int>& targets, SignConfig& cfg, bool stable) = 0;
     virtual Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) = 0;
     virtual Ct hybrid(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk, int variant) = 0;
     virtual Ct place2N(const Ct& rank, const Ct& in) = 0;
@@ -126,6 +129,7 @@ struct Sorter : SorterBase {
         if (!bs) bs = std::make_unique<BitonicSort<N>>(cc_, pk_, rot_, enc_);
         return bs->sort(in, SignFunc::CompositeSign, cfg);
     }
+    uint32_t size() const override { return (uint32_t)N; }
     Ct sort(const Ct& in, SignConfig& cfg) override { return ds.sort(in, SignFunc::CompositeSign, cfg); }
     Ct rank(const Ct& in, SignConfig& cfg) override {
         return ds.constructRank(in, SignFunc::CompositeSign, cfg);
@@ -142,6 +146,12 @@ struct Sorter : SorterBase {
         return ds.sortRecords(keys, cols, SignFunc::CompositeSign, cfg, stable);
     }
     size_t recordsGraphNodes() const override { return ds.recordsGraphNodes(); }
+    Ct selectRanks(const Ct& r, const Ct& in, const std::vector<int>& targets) override {
+        return ds.selectRanks(r, in, targets);
+    }
+    Ct select(const Ct& in, const std::vector<int>& targets, SignConfig& cfg, bool stable) override {
+        return ds.select(in, targets, SignFunc::CompositeSign, cfg, stable);
+    }
     Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) override {
         return ds.sort_hybrid1(in, SignFunc::CompositeSign, cfg, sk);
     }
@@ -393,6 +403,15 @@ int sfhe_place_counts(sfhe_ctx* c, uint64_t* hits, uint64_t* columns, uint64_t* 
     return SFHE_OK;
 }
 
+int sfhe_select_counts(sfhe_ctx* c, uint64_t* batches, uint64_t* fold_fused, uint64_t* fold_composed) {
+    REQUIRE(c && batches && fold_fused && fold_composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *batches = s.select_batches;
+    *fold_fused = s.fold_fused;
+    *fold_composed = s.fold_composed;
+    return SFHE_OK;
+}
+
 int sfhe_const_term_counts(sfhe_ctx* c, uint64_t* merged, uint64_t* single, uint64_t* composed) {
     REQUIRE(c && merged && single && composed, "null argument");
     auto s = c->cc->GetOpStats();
@@ -470,6 +489,11 @@ int sfhe_eval_rotate_sum(sfhe_ctx* c, const sfhe_ct* const* a, const int32_t* r,
         *out = wrap(c->cc->EvalRotateSum(v, std::vector<int32_t>(r, r + count)));
     });
 }
+int sfhe_eval_rotate_fold(sfhe_ctx* c, const sfhe_ct* a, int32_t stride, uint32_t count, sfhe_ct** out) {
+    REQUIRE(c && a && out, "null argument");
+    REQUIRE(count >= 2 && count <= 8, "count must be in [2, 8]");
+    return guard([&] { *out = wrap(c->cc->EvalRotateFold(a->ct, stride, count)); });
+}
 int sfhe_bootstrap_setup(sfhe_ctx* c, uint32_t budget_c2s, uint32_t budget_s2c, uint32_t slots) {
     REQUIRE(c, "null argument");
     REQUIRE(c->keys.secretKey, "sfhe_keygen must be called first");
@@ -519,6 +543,24 @@ int sfhe_direct_sort_params(uint32_t N, uint32_t* depth, int32_t* rot, size_t ca
         if (depth) *depth = (uint32_t)p->multDepth;
         if (count) *count = r.size();
         for (size_t i = 0; i < r.size() && i < cap && rot; ++i) rot[i] = r[i];
+    });
+}
+
+int sfhe_select_params(uint32_t N, uint32_t* depth, int32_t* rot, size_t cap, size_t* count) {
+    const sfhe::SizeParams* p = sfhe::sizeParams((int)N);
+    REQUIRE(p && validN(N), "N has no selection parameters (a power of two in [4, 1024])");
+    return guard([&] {
+        // the sort's keys united with the radix-4 fold amounts {s, 2s, 3s : s = 4^i < N}
+        std::set<int> r(p->rotations.begin(), p->rotations.end());
+        for (int s = 1; s < (int)N; s *= 4)
+            for (int k = 1; k <= 3; ++k) r.insert(k * s);
+        if (depth) *depth = (uint32_t)p->multDepth;
+        if (count) *count = r.size();
+        size_t i = 0;
+        for (int v : r) {
+            if (i >= cap || !rot) break;
+            rot[i++] = v;
+        }
     });
 }
 
@@ -625,6 +667,39 @@ int sfhe_sorter_sort_records(sfhe_sorter* s, sfhe_ct* keys, sfhe_ct* const* cols
         auto sorted = s->impl->sortRecords(keys->ct, in, cfg, stable != 0);
         *keys_out = wrap(sorted[0]);
         for (size_t i = 0; i < count; ++i) outs[i] = wrap(sorted[i + 1]);
+    });
+}
+
+static int selectTargets(const sfhe_sorter* s, const uint32_t* targets, size_t count, uint32_t N,
+                         std::vector<int>* out) {
+    (void)s;
+    REQUIRE(count >= 1 && count <= N, "target count out of range (1 .. N)");
+    std::vector<char> seen(N, 0);
+    for (size_t i = 0; i < count; ++i) {
+        REQUIRE(targets[i] < N, "target rank out of range (0 .. N - 1)");
+        REQUIRE(!seen[targets[i]], "duplicate target rank");
+        seen[targets[i]] = 1;
+        out->push_back((int)targets[i]);
+    }
+    return SFHE_OK;
+}
+
+int sfhe_sorter_select_ranked(sfhe_sorter* s, const sfhe_ct* rank, const sfhe_ct* in, const uint32_t* targets,
+                              size_t count, sfhe_ct** out) {
+    REQUIRE(s && rank && in && targets && out, "null argument");
+    std::vector<int> t;
+    if (int rc = selectTargets(s, targets, count, s->impl->size(), &t)) return rc;
+    return guard([&] { *out = wrap(s->impl->selectRanks(rank->ct, in->ct, t)); });
+}
+
+int sfhe_sorter_select(sfhe_sorter* s, const sfhe_ct* in, const uint32_t* targets, size_t count, int stable, int n,
+                       int dg, int df, sfhe_ct** out) {
+    REQUIRE(s && in && targets && out, "null argument");
+    std::vector<int> t;
+    if (int rc = selectTargets(s, targets, count, s->impl->size(), &t)) return rc;
+    return guard([&] {
+        auto cfg = cfgOf(n, dg, df);
+        *out = wrap(s->impl->select(in->ct, t, cfg, stable != 0));
     });
 }
 

@@ -3803,6 +3803,114 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalRotateSum(const std::vecto
     return res;
 }
 
+// sum_{k < count} Rot(a, k * stride): the rotating terms share the ModUp of a's
+// c1 (hoisting), their key inner products are summed in the extended basis and
+// share one ModDown (output aggregation) -- the two savings EvalFastRotation
+// and EvalRotateSum give separately.  With acc = sum_k <sigma_k(ext), key_k>:
+//   c0' = sum_k sigma_k(c0) + ModDown(acc)_0,  c1' = ModDown(acc)_1,
+// plus `a` once per identity term.  Fused: acc is one sfp_ks_inner_aut_sum
+// launch; composed: per term sfp_automorph of the digits, then sfp_ks_inner
+// (first) / sfp_ks_inner_acc.  Both leave the canonical residue of the same
+// integer sum in acc, so everything after it is identical.
+Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalRotateFold(const Ciphertext<DCRTPoly>& a, int32_t stride,
+                                                                 uint32_t count) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    if (!a) SFHE_THROW("EvalRotateFold: null ciphertext");
+    if (count < 2 || count > 8) SFHE_THROW("EvalRotateFold: count must be in [2, 8], got " + std::to_string(count));
+    SfheInternal::deps(s, {&a});  // (canonical rows: a pending product is rescaled first)
+    const int64_t slots = a->slots ? (int64_t)a->slots : (int64_t)s->n / 2;
+    std::vector<int32_t> amounts;
+    std::vector<uint32_t> gals;
+    uint32_t ident = 0;
+    for (uint32_t k = 0; k < count; ++k) {
+        // (the packing is `slots`-periodic: an amount acts as its residue modulo the slot count)
+        const int64_t r = (((int64_t)k * stride) % slots + slots) % slots;
+        if (r == 0 || GaloisForRotation((int32_t)r) == 1) {
+            ++ident;
+            continue;
+        }
+        const uint32_t gal = GaloisForRotation((int32_t)r);
+        if (!s->rotKeys.count(gal))
+            SFHE_THROW("EvalRotateFold: EvalKey for rotation " + std::to_string(r) + " is not found");
+        amounts.push_back((int32_t)r);
+        gals.push_back(gal);
+    }
+    Ciphertext<DCRTPoly> res;
+    if (!gals.empty()) {
+        const uint32_t R = (uint32_t)gals.size();
+        const uint32_t level = a->level, ell = SfheInternal::ctEll(s, *a), n = s->n;
+        auto pre = EvalFastRotationPrecompute(a);
+        const bool shard = s->shardAt(ell);
+        // the terms' keys of the digits' special-prime tier (EvalFastRotation's rule)
+        std::vector<const DeviceBufferPtr*> keys;
+        for (uint32_t gal : gals) {
+            const DeviceBufferPtr* key = s->rotFor(gal, ell);
+            if (!shard && (size_t)(ell + s->Kof((*key)->ksTier)) * n != pre->stride) key = &s->rotKeys.at(gal);
+            keys.push_back(key);
+        }
+        const int tier = (*keys[0])->ksTier;
+        for (auto* k : keys)
+            if ((*k)->ksTier != tier) SFHE_THROW("internal: rotation keys of different special-prime tiers");
+        const uint32_t K = s->Kof(tier), beta = pre->beta;
+        const size_t stride_ = pre->stride;
+        if (!shard && stride_ != (size_t)(ell + K) * n)
+            SFHE_THROW("internal: extended digits of another special-prime tier");
+        auto out = SfheInternal::newCt(this, level, a->slots);
+        // c0' = sum_k sigma_k(c0): one permutation per term, summed by one weighted sum (weights 1)
+        std::vector<DeviceBufferPtr> c0s;
+        for (uint32_t k = 0; k < R; ++k) {
+            if (k) c0s.push_back(s->alloc((size_t)s->rows(ell) * n));
+            sfp_automorph(s->dev, k ? c0s.back()->ptr : out->c0, a->c0, gals[k], st->qmap(ell));
+        }
+        if (!c0s.empty()) {
+            std::vector<const uint64_t*> ins{out->c0};
+            for (auto& b : c0s) ins.push_back(b->ptr);
+            const std::vector<uint64_t> ones(ins.size() * s->rows(ell), 1);
+            sfp_lin_wsum(s->dev, out->c0, ins.data(), ones.data(), (uint32_t)ins.size(), st->qmap(ell));
+        }
+        auto acc = s->alloc(2 * stride_);
+        s->dep(pre->ext.get());
+        const char* knob = std::getenv("SFHE_SELECT_FOLD");  // (read per call: tests switch it)
+        bool fused = false;
+        if (sfp_ks_inner_aut_sum && !(knob && *knob == '0') && !shard) {
+            std::vector<const uint64_t*> kp;
+            for (auto* k : keys) kp.push_back((*k)->ptr);
+            fused = sfp_ks_inner_aut_sum(s->dev, acc->ptr, acc->ptr + stride_, pre->ext->ptr, stride_, kp.data(),
+                                         gals.data(), R, beta, ell, K, s->Lq) == 0;
+        }
+        if (!fused) {
+            auto ext = s->alloc(stride_ * beta);
+            // one permutation launch over every digit's rows (the map is prime-independent)
+            const uint32_t rows = beta * (uint32_t)(stride_ / n);
+            for (uint32_t k = 0; k < R; ++k) {
+                sfp_automorph(s->dev, ext->ptr, pre->ext->ptr, gals[k], sfp_limbs{rows, rows, 0, 0});
+                if (shard)
+                    SfheInternal::innerShard(s, acc->ptr, ext->ptr, stride_, beta, ell, *keys[k], k ? 1 : 0);
+                else
+                    (k ? sfp_ks_inner_acc : sfp_ks_inner)(s->dev, acc->ptr, acc->ptr + stride_, ext->ptr, stride_,
+                                                          (*keys[k])->ptr, beta, ell, K, s->Lq);
+            }
+        }
+        if (shard) {
+            SfheInternal::modDownShard(s, acc->ptr, ell, out->c0, out->c1, 1, 0);
+        } else {
+            auto md = s->alloc((size_t)2 * ell * n);
+            sfp_moddown2(s->dev, out->c0, out->c1, acc->ptr, stride_, ell, K, s->Lq, s->moddownConvOf(tier),
+                         s->pInvModQof(tier), 1, 0, md->ptr, 0);
+        }
+        (fused ? s->stats.fold_fused : s->stats.fold_composed)++;
+        s->stats.keyswitch += R;
+        s->stats.automorph += R;
+        s->countBytes((3.0 * ell * R + (2.0 * R + 1.0) * beta * (stride_ / n)) * n * 8);
+        res = SfheInternal::traced(this, out, "EvalRotateFold");
+    }
+    for (uint32_t k = 0; k < ident; ++k) res = res ? EvalAdd(res, a) : a->Clone();
+    return res;
+}
+
+void CryptoContextImpl<DCRTPoly>::NoteSelection(uint64_t batches) { st->stats.select_batches += batches; }
+
 // Double hoisting (Bossuat et al.'s hoisted ModDown): with acc_k the
 // extended-basis inner product of rotation k, p (.) ModDown(acc_k) and
 // ModDown(p_ext (.) acc_k) are the same value up to the ModDown rounding, so

@@ -450,6 +450,23 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     // ModDown rounding instead of one per term.  Every r_k needs its own key.
     Ciphertext<DCRTPoly> EvalRotateSum(const std::vector<Ciphertext<DCRTPoly>>& a,
                                        const std::vector<int32_t>& r);
+    // Engine extension (the selection's in-partition sums):
+    // sum_{k < count} EvalRotate(a, k * stride), 2 <= count <= 8, with ONE
+    // ModUp (the rotations of one ciphertext share its extended digits, as
+    // EvalFastRotation), the key inner products of all rotating terms summed in
+    // the extended basis and ONE ModDown (as EvalRotateSum).  Term 0 is `a`
+    // itself, and a term whose amount is a multiple of the slot count is added
+    // as it is; every other amount needs its own rotation key (the error names
+    // the amount).  Where the backend has prims.h sfp_ks_inner_aut_sum the
+    // inner products are one launch that reads the digits through every
+    // automorphism; elsewhere (the C oracle, SFHE_SELECT_FOLD=0 -- read per
+    // call --, a level whose rows are dealt over ranks, the prim declining) each
+    // term permutes the digits (sfp_automorph) and accumulates
+    // (sfp_ks_inner / sfp_ks_inner_acc): the same residues.  OpStats
+    // fold_fused / fold_composed count the calls of each kind.
+    Ciphertext<DCRTPoly> EvalRotateFold(const Ciphertext<DCRTPoly>& a, int32_t stride, uint32_t count);
+    // a selection ran `batches` indicator batches (OpStats)
+    void NoteSelection(uint64_t batches);
     // Engine extension (double hoisting): sum_t sum_k p_tk (.) EvalRotate(a_t, r_tk), then one
     // rescale -- EvalMultAddPlain over hoisted rotations.  Each input's rotations share one
     // ModUp; every key-switched term is multiplied by its plaintext in the extended basis Q*P
@@ -677,6 +694,9 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         // multi-column placements: indicators evaluated, columns they served, giant-step sums formed
         // by sfp_mac_plain2_cols / left to the per-column path
         uint64_t place_hits = 0, place_columns = 0, place_fused = 0, place_composed = 0;
+        // selections: indicator batches run; EvalRotateFold calls whose inner products were one
+        // launch (sfp_ks_inner_aut_sum) / composed of the generic prims
+        uint64_t select_batches = 0, fold_fused = 0, fold_composed = 0;
     };
     OpStats GetOpStats() const;
     void ResetOpStats();
@@ -759,7 +779,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 9
+#define SFHE_FACADE_ABI_VERSION 10
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

@@ -3837,6 +3837,79 @@ __global__ __launch_bounds__(kThreads) void k_ks_inner(const ArgSet<KsInnerArgs,
     }
 }
 
+// The key inner products of R rotations of ONE ciphertext, summed (prims.h
+// sfp_ks_inner_aut_sum; EvalRotateFold):
+//   acc_p = sum_k sum_j sigma_k(ext_j) (.) key_k,p,j   (k < R, j < beta)
+// The shared extended digits are read through each automorphism at the source
+// index k_automorph maps a coefficient from (as k_ks_inner does for one gal):
+// R 8-byte gathers per digit word and coefficient, the keys as 16-byte loads,
+// no permuted copy and no accumulator round trip between the terms.  The R
+// key pointers and Galois elements travel by value in the argument block.
+// Accumulator bound: every product of two canonical residues of primes of at
+// most SF_MAX_PRIME_BITS = 60 bits is below 2^120, so R * beta <= 2^8 of them
+// fit the 128-bit accumulator; the prim declines more.  One reduction at the
+// end gives the canonical residue of the sum, which is what R reduced inner
+// products added modulo q (sfp_ks_inner + sfp_ks_inner_acc) give.
+struct KsFoldArgs {
+    u64 *acc0, *acc1;
+    const u64* ext;
+    size_t extStride;
+    const u64* key[SFP_FOLD_MAX];
+    uint32_t gal[SFP_FOLD_MAX];
+    uint32_t R, beta, ell, rows, Lq, keyRows;
+};
+static_assert(sizeof(KsFoldArgs) + sizeof(const sf_barrett*) + sizeof(uint32_t) <= 4096,
+              "k_ks_inner_aut_sum: the arguments exceed the 4 KB kernel-argument block");
+static_assert(SF_MAX_PRIME_BITS * 2 + 8 <= 128, "k_ks_inner_aut_sum: 2^8 products of 2^120 must fit 128 bits");
+constexpr uint32_t kFoldMaxProducts = 256;  // R * beta
+__global__ __launch_bounds__(kThreads) void k_ks_inner_aut_sum(const KsFoldArgs A, const sf_barrett* __restrict__ bar,
+                                                               uint32_t logn) {
+    u64* __restrict__ acc0 = A.acc0;
+    u64* __restrict__ acc1 = A.acc1;
+    const u64* __restrict__ ext = A.ext;
+    const size_t extStride = A.extStride;
+    const uint32_t R = A.R, beta = A.beta, ell = A.ell, NP = A.keyRows;
+    // two coefficients per thread: 16-byte loads of every key row and stores
+    const size_t pairs = ((size_t)A.rows << logn) >> 1;
+    const uint32_t n = 1u << logn;
+    const u64 mask = 2ull * n - 1;
+    for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < pairs; i += (size_t)gridDim.x * kThreads) {
+        const size_t e = 2 * i;
+        const uint32_t t = (uint32_t)(e >> logn);
+        const uint32_t x = (uint32_t)(e & (n - 1));
+        // ext row t: prime t (q rows) or Lq + (t - ell) (P rows), which is also its key row
+        const uint32_t kr = t < ell ? t : A.Lq + (t - ell);
+        const sf_barrett B = loadBar(bar, kr);
+        const size_t row = e - x;
+        const u64 b0 = 2ull * sf_brev(x, logn) + 1, b1 = 2ull * sf_brev(x + 1, logn) + 1;
+        Acc s0{0, 0}, s0b{0, 0}, s1{0, 0}, s1b{0, 0};
+        for (uint32_t k = 0; k < R; ++k) {
+            const u64 g = A.gal[k];
+            const size_t src0 = row + sf_brev((uint32_t)(((b0 * g & mask) - 1) >> 1), logn);
+            const size_t src1 = row + sf_brev((uint32_t)(((b1 * g & mask) - 1) >> 1), logn);
+            const u64* __restrict__ key = A.key[k];
+            for (uint32_t j = 0; j < beta; ++j) {
+                const u64 ex = ext[j * extStride + src0];
+                const u64 ey = ext[j * extStride + src1];
+                const u64* kb = key + (size_t)j * 2 * NP * n + ((size_t)kr << logn) + x;
+                const ulonglong2 b2 = *reinterpret_cast<const ulonglong2*>(kb);
+                const ulonglong2 a2 = *reinterpret_cast<const ulonglong2*>(kb + (size_t)NP * n);
+                macc(s0, ex, b2.x);
+                macc(s0b, ey, b2.y);
+                macc(s1, ex, a2.x);
+                macc(s1b, ey, a2.y);
+            }
+        }
+        ulonglong2 o0, o1;
+        o0.x = sf_reduce128_acc(s0.lo, s0.hi, &B);
+        o0.y = sf_reduce128_acc(s0b.lo, s0b.hi, &B);
+        o1.x = sf_reduce128_acc(s1.lo, s1.hi, &B);
+        o1.y = sf_reduce128_acc(s1b.lo, s1b.hi, &B);
+        *reinterpret_cast<ulonglong2*>(acc0 + e) = o0;
+        *reinterpret_cast<ulonglong2*>(acc1 + e) = o1;
+    }
+}
+
 // ============================================================================
 // sampling / loading
 
@@ -6484,6 +6557,46 @@ void sfp_ks_inner_acc(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_t
                                 KsInnerArgs{acc0, acc1, ext, extStride, key, beta, sfp_limbs{ell + K, ell, Lq, 0, 1}, keyQ0, keyRows0, (const u64*)nullptr, (const u64*)nullptr, (u64)0, 1, (const u64*)nullptr, d->kg, 0u});
     });
     checkLaunch(d, "ks_inner_acc");
+}
+
+int sfp_ks_inner_aut_sum(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_t* ext, size_t extStride,
+                         const uint64_t* const* keys, const uint32_t* gals, uint32_t R, uint32_t beta, uint32_t ell,
+                         uint32_t K, uint32_t Lq) {
+    // declined (nothing done): more terms than the argument block holds or more
+    // products than the accumulator, a sliced key (limb sharding), rows the
+    // 16-byte accesses cannot take, digits shorter than the rows read
+    if (!R || R > SFP_FOLD_MAX || !beta || R * beta > kFoldMaxProducts || d->kg.rows || d->n < 2) return -1;
+    if (!ell || ell > Lq || ell + K > SFP_MAX_LIMBS || Lq + K > d->np || extStride < (size_t)(ell + K) * d->n)
+        return -1;
+    uintptr_t bits = (uintptr_t)acc0 | (uintptr_t)acc1 | (uintptr_t)ext | (uintptr_t)(extStride * 8);
+    for (uint32_t k = 0; k < R; ++k) {
+        bits |= (uintptr_t)keys[k];
+        if (!keys[k] || !(gals[k] & 1) || gals[k] >= 2 * d->n) return -1;
+    }
+    if (bits & 15) return -1;
+    KsFoldArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.acc0 = acc0;
+    a.acc1 = acc1;
+    a.ext = ext;
+    a.extStride = extStride;
+    for (uint32_t k = 0; k < R; ++k) {
+        a.key[k] = keys[k];
+        a.gal[k] = gals[k];
+    }
+    a.R = R;
+    a.beta = beta;
+    a.ell = ell;
+    a.rows = ell + K;
+    a.Lq = Lq;
+    a.keyRows = Lq + K;
+    const size_t total = (size_t)(ell + K) * d->n;
+    // reads R * beta gathered ext words and 2 * R * beta key rows, writes 2 accumulator rows, per limb
+    timedLaunch(d, SFP_FAM_KSINNER, 8.0 * total * (3.0 * R * beta + 2.0), [&] {
+        SFP_GO(k_ks_inner_aut_sum, dim3(ewGrid(total / 2)), dim3(kThreads), a, d->bar, d->logn);
+    });
+    checkLaunch(d, "ks_inner_aut_sum");
+    return 0;
 }
 
 void sfp_ks_inner_mul(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_t* ext, size_t extStride,

@@ -395,6 +395,24 @@ SFP_OPTIONAL int sfp_mac_plain2_cols(sfp_dev* d, uint64_t* const* out0, uint64_t
                                      const uint64_t* const* a0, const uint64_t* const* a1, const uint64_t* const* b,
                                      uint32_t nin, uint32_t ng, uint32_t nc, sfp_limbs m);
 
+// ---- optional: the key inner products of several rotations of one ciphertext ----
+// acc_p = sum_k sum_j sigma_k(ext_j) (.) key_k,p,j for R <= SFP_FOLD_MAX pairs
+// (Galois element gals[k], switching key keys[k]) over the SHARED extended
+// digits ext (as sfp_ks_inner_aut reads them for one gal): one launch, every
+// product of the R terms in the 128-bit accumulators, one reduction.  The
+// canonical residues of sfp_automorph of the digits + sfp_ks_inner for the
+// first term and + sfp_ks_inner_acc for the others (R permuted copies and R
+// launches, the accumulators read back R - 1 times).  keys and gals are host
+// arrays that travel in the kernel's arguments: no upload and no host
+// synchronisation, so the prim may be captured and issued on any lane.  Weak
+// like the prims above: where its address is null (the C oracle) or it returns
+// -1 (nothing done: R or R * beta too large, rows not 16-byte aligned, a
+// sliced key geometry) the host layer runs the composed form.
+#define SFP_FOLD_MAX 7
+SFP_OPTIONAL int sfp_ks_inner_aut_sum(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_t* ext,
+                                      size_t ext_stride, const uint64_t* const* keys, const uint32_t* gals,
+                                      uint32_t R, uint32_t beta, uint32_t ell, uint32_t K, uint32_t Lq);
+
 // ---- optional: CKKS decoding on the device (the end of a decryption) ----------
 // `count` row sets src + b * srcStride, each nl (1 or 2) COEFFICIENT-domain
 // rows of n words modulo primes 0 .. nl-1 (c0 + c1 s after its inverse NTT),

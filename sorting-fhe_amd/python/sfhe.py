@@ -51,6 +51,8 @@ ABI_SYMBOLS = [
     "sfhe_sorter_sort_stable", "sfhe_sorter_rank_stable", "sfhe_tie_counts",
     "sfhe_const_term_counts",
     "sfhe_sorter_place_many", "sfhe_sorter_sort_records", "sfhe_sorter_records_graph_nodes", "sfhe_place_counts",
+    "sfhe_select_params", "sfhe_sorter_select_ranked", "sfhe_sorter_select", "sfhe_eval_rotate_fold",
+    "sfhe_select_counts",
 ]
 
 MAX_COLUMNS = 8  # SFHE_MAX_COLUMNS
@@ -185,6 +187,11 @@ _SIGS = {
     "sfhe_sorter_records_graph_nodes": (C.c_int, [_VP, _PU64]),
     "sfhe_place_counts": (C.c_int, [_VP, _PU64, _PU64, _PU64, _PU64]),
     "sfhe_const_term_counts": (C.c_int, [_VP, _PU64, _PU64, _PU64]),
+    "sfhe_select_params": (C.c_int, [_U32, _PU32, _PI32, _SZ, _PSZ]),
+    "sfhe_sorter_select_ranked": (C.c_int, [_VP, _VP, _VP, _PU32, _SZ, _PVP]),
+    "sfhe_sorter_select": (C.c_int, [_VP, _VP, _PU32, _SZ, C.c_int, C.c_int, C.c_int, C.c_int, _PVP]),
+    "sfhe_eval_rotate_fold": (C.c_int, [_VP, _VP, C.c_int32, _U32, _PVP]),
+    "sfhe_select_counts": (C.c_int, [_VP, _PU64, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -542,6 +549,19 @@ class Engine:
         rs = (C.c_int32 * len(rots))(*[int(r) for r in rots])
         return self._new(self.lib.sfhe_eval_rotate_sum, self.ctx, hs, rs, len(cts))
 
+    def rotate_fold(self, a, stride: int, count: int):
+        """sum_{k < count} rotate(a, k * stride), 2 <= count <= 8, with one ModUp and one ModDown
+        (EvalRotateFold); every amount that is no multiple of a's slot count needs its key."""
+        return self._new(self.lib.sfhe_eval_rotate_fold, self.ctx, a.h, int(stride), int(count))
+
+    def select_counts(self):
+        """(batches, fold_fused, fold_composed) since the last op_stats reset: indicator batches
+        the selections ran, rotate_fold calls (the selections' included) whose inner products
+        were one launch / composed of the generic primitives."""
+        v = [C.c_uint64() for _ in range(3)]
+        self._chk(self.lib.sfhe_select_counts(self.ctx, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def bootstrap_setup(self, level_budget=(5, 5), slots: int = 0):
         """EvalBootstrapSetup + EvalBootstrapKeyGen for `slots`-slot ciphertexts."""
         self._chk(self.lib.sfhe_bootstrap_setup(self.ctx, level_budget[0], level_budget[1], slots))
@@ -685,6 +705,33 @@ class Sorter:
                                                             df, C.byref(k), outs))
         return Ct(self.eng, k), [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cts))]
 
+    @staticmethod
+    def _targets(targets):
+        t = [int(x) for x in targets]
+        if any(x < 0 for x in t):
+            raise SfheError("sfhe error -1: target rank out of range (0 .. N - 1)")
+        return (C.c_uint32 * max(len(t), 1))(*t), len(t)
+
+    def select_ranked(self, rank: Ct, ct: Ct, targets) -> Ct:
+        """Slot i < len(targets) of the N-slot result holds the element of `ct` whose rank (in
+        `rank`: rank() / rank_stable() of ct or of a key column) is targets[i]; the other slots
+        hold 0 up to noise.  Distinct ranks in [0, N).  Needs the rotations of select_params."""
+        buf, k = self._targets(targets)
+        return self.eng._new(self.eng.lib.sfhe_sorter_select_ranked, self.h, rank.h, ct.h, buf, k)
+
+    def select(self, ct: Ct, targets, stable: bool = False, n: int = 3, dg: int = 2, df: int = 2) -> Ct:
+        """rank (stable: rank_stable, one level more) of ct, then select_ranked; always eager."""
+        buf, k = self._targets(targets)
+        return self.eng._new(self.eng.lib.sfhe_sorter_select, self.h, ct.h, buf, k, int(bool(stable)), n, dg, df)
+
+    def top_k(self, ct: Ct, k: int, largest: bool = False, **kw) -> Ct:
+        """The k smallest values in ascending order (largest: the k largest, descending)."""
+        return self.select(ct, [self.N - 1 - i for i in range(k)] if largest else list(range(k)), **kw)
+
+    def kth(self, ct: Ct, t: int, **kw) -> Ct:
+        """The element of rank t (0 = the minimum, N - 1 = the maximum, N // 2 = the upper median) in slot 0."""
+        return self.select(ct, [t], **kw)
+
     def records_graph_nodes(self) -> int:
         v = C.c_uint64()
         self.eng._chk(self.eng.lib.sfhe_sorter_records_graph_nodes(self.h, C.byref(v)))
@@ -739,6 +786,20 @@ def direct_sort_params(N: int, backend: str = "hip"):
         raise SfheError(lib.sfhe_last_error().decode())
     buf = (C.c_int32 * cnt.value)()
     lib.sfhe_direct_sort_params(N, None, buf, cnt.value, None)
+    return depth.value, list(buf)
+
+
+def select_params(N: int, backend: str = "hip"):
+    """(depth, rotations) for Sorter.select: direct_sort_params united with the radix-4 fold
+    amounts {s, 2s, 3s : s = 4^i < N}."""
+    lib = load(backend)
+    depth = C.c_uint32()
+    cnt = C.c_size_t()
+    rc = lib.sfhe_select_params(N, C.byref(depth), None, 0, C.byref(cnt))
+    if rc != SFHE_OK:
+        raise SfheError(lib.sfhe_last_error().decode())
+    buf = (C.c_int32 * cnt.value)()
+    lib.sfhe_select_params(N, None, buf, cnt.value, None)
     return depth.value, list(buf)
 
 
