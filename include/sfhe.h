@@ -33,7 +33,9 @@ extern "C" {
  * the record sort: SFHE_MAX_COLUMNS, sfhe_sorter_place_many,
  * sfhe_sorter_sort_records, sfhe_sorter_records_graph_nodes, sfhe_place_counts,
  * and the selection: sfhe_select_params, sfhe_sorter_select_ranked,
- * sfhe_sorter_select, sfhe_eval_rotate_fold, sfhe_select_counts) */
+ * sfhe_sorter_select, sfhe_eval_rotate_fold, sfhe_select_counts, and the
+ * record selection: sfhe_sorter_select_many, sfhe_sorter_select_records,
+ * sfhe_eval_rotate_fold_many, sfhe_select_cols_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -128,6 +130,12 @@ int sfhe_place_counts(sfhe_ctx* c, uint64_t* hits, uint64_t* columns, uint64_t* 
  * sfhe_eval_rotate_fold calls (the selections' included) whose inner products
  * were one launch / were composed of the generic primitives. */
 int sfhe_select_counts(sfhe_ctx* c, uint64_t* batches, uint64_t* fold_fused, uint64_t* fold_composed);
+/* Since the last sfhe_op_stats reset: columns the multi-column selections
+ * served, launches sfhe_eval_rotate_fold_many issued through
+ * sfp_ks_inner_aut_sum_cols, and columns it passed to sfhe_eval_rotate_fold's
+ * path (SFHE_SELECT_COLS=0, read per call, takes the latter; the results are
+ * bit-identical). */
+int sfhe_select_cols_counts(sfhe_ctx* c, uint64_t* columns, uint64_t* fused, uint64_t* composed);
 /* Small polynomials (an encryption's v, e0, e1; the keys' errors and secret)
  * sampled on the device (sfp_sample_small) and on the host since the last
  * sfhe_op_stats reset (SFHE_DEV_SAMPLE=0, read per call, samples on the host;
@@ -221,6 +229,14 @@ int sfhe_eval_rotate_sum(sfhe_ctx* c, const sfhe_ct* const* a, const int32_t* r,
  * amount needs its rotation key (SFHE_ESCHEME; the message names the amount).
  * count outside [2, 8]: SFHE_EINVAL. */
 int sfhe_eval_rotate_fold(sfhe_ctx* c, const sfhe_ct* a, int32_t stride, uint32_t count, sfhe_ct** out);
+/* outs[i] = sfhe_eval_rotate_fold(cts[i], stride, count), residue for residue,
+ * for ncts >= 1 ciphertexts at one level and slot count (else SFHE_ESCHEME):
+ * on the device the inner products of up to 16 of them are tiles of columns
+ * that read each rotation-key word once (SFHE_SELECT_COLS=0, read per call,
+ * or more than 16: sfhe_eval_rotate_fold per ciphertext).  ncts = 0, a NULL
+ * entry, count outside [2, 8]: SFHE_EINVAL. */
+int sfhe_eval_rotate_fold_many(sfhe_ctx* c, const sfhe_ct* const* cts, size_t ncts, int32_t stride, uint32_t count,
+                               sfhe_ct** outs);
 /* CKKS bootstrapping (OpenFHE's EvalBootstrapSetup + EvalBootstrapKeyGen and
  * EvalBootstrap, as src/k-way/EvalUtils.cpp:57-86 and src/sort_algo.h:1437
  * call them): setup for ciphertexts of `slots` slots with the level budget
@@ -322,6 +338,21 @@ int sfhe_sorter_select_ranked(sfhe_sorter* s, const sfhe_ct* rank, const sfhe_ct
                               size_t count, sfhe_ct** out);
 int sfhe_sorter_select(sfhe_sorter* s, const sfhe_ct* in, const uint32_t* targets, size_t count, int stable, int n,
                        int dg, int df, sfhe_ct** out);
+/* Engine extensions (additions at ABI 3): selection of records -- ORDER BY key
+ * LIMIT k over rows.  sfhe_sorter_select_many: outs[i] holds the residues of
+ * sfhe_sorter_select_ranked(rank, cols[i], targets), 1 <= ncols <=
+ * SFHE_MAX_COLUMNS columns at one level (else SFHE_ESCHEME); the indicator of
+ * a batch is evaluated once for all columns.  sfhe_sorter_select_records
+ * computes the (stable != 0: stable) rank of `keys` first and selects the keys
+ * and 0 <= ncols <= SFHE_MAX_COLUMNS payload columns by it: *keys_out is
+ * sfhe_sorter_select's result, outs[i] column i's rows in the same order.
+ * Targets, depth and rotation keys as sfhe_sorter_select_ranked; a NULL entry
+ * or a column count out of range: SFHE_EINVAL.  Always eager. */
+int sfhe_sorter_select_many(sfhe_sorter* s, const sfhe_ct* rank, const sfhe_ct* const* cols, size_t ncols,
+                            const uint32_t* targets, size_t count, sfhe_ct** outs);
+int sfhe_sorter_select_records(sfhe_sorter* s, const sfhe_ct* keys, const sfhe_ct* const* cols, size_t ncols,
+                               const uint32_t* targets, size_t count, int stable, int n, int dg, int df,
+                               sfhe_ct** keys_out, sfhe_ct** outs);
 /* nodes of the captured record sort (0 while none); sfhe_sorter_graph_nodes
  * keeps reporting the plain / stable sort's graph */
 int sfhe_sorter_records_graph_nodes(const sfhe_sorter* s, uint64_t* nodes);

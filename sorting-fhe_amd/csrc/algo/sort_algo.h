@@ -21,6 +21,8 @@
 // Records: placeMany places several columns by one rank with
 // the indicator evaluated once per batch, sortRecords = the (stable) rank of
 // a key column + placeMany of the keys and their payload columns.
+// Record selection: selectRanksMany / selectRecords select the
+// rows of chosen ranks, likewise with one indicator per batch for all columns.
 //
 // Engine-specific scheduling (identical slot values, fewer key switches):
 //   * baby-step rotations of one ciphertext share one hoisted ModUp;
@@ -772,8 +774,8 @@ class DirectSort : public SortBase<N> {
         return x;
     }
 
-    Ciphertext<DCRTPoly> selectRanks(const Ciphertext<DCRTPoly>& ctx_Rank, const Ciphertext<DCRTPoly>& input_array,
-                                     const std::vector<int>& targets) {
+    // the checks every selection runs first: the target list, and the depth a rank at this level needs
+    int selectCheck(const Ciphertext<DCRTPoly>& ctx_Rank, const std::vector<int>& targets) {
         const int K = (int)targets.size();
         if (K < 1 || K > N) throw std::invalid_argument("select: the target count must be in [1, N]");
         {
@@ -791,6 +793,13 @@ class DirectSort : public SortBase<N> {
             throw OpenFHEException("select: needs multiplicative depth " + std::to_string(need) +
                                    " from a rank at level " + std::to_string(ctx_Rank->GetLevel()) +
                                    "; the context has " + std::to_string(m_cc->GetMultiplicativeDepth()));
+        return ps;
+    }
+
+    Ciphertext<DCRTPoly> selectRanks(const Ciphertext<DCRTPoly>& ctx_Rank, const Ciphertext<DCRTPoly>& input_array,
+                                     const std::vector<int>& targets) {
+        const int ps = selectCheck(ctx_Rank, targets);
+        const int K = (int)targets.size();
         const sfhe::RankLayout L(N, max_batch);
         sfhe::PhaseTimer ph(m_cc);
         int Psel = 1;
@@ -874,6 +883,131 @@ class DirectSort : public SortBase<N> {
                                 SignFunc SignFunc, SignConfig& Cfg, bool stable) {
         auto rank = stable ? constructRankStable(input_array, SignFunc, Cfg) : constructRank(input_array, SignFunc, Cfg);
         return selectRanks(rank, input_array, targets);
+    }
+
+    // foldPartitions of several columns of one level (EvalRotateFoldMany per step)
+    std::vector<Ciphertext<DCRTPoly>> foldPartitionsMany(std::vector<Ciphertext<DCRTPoly>> x) {
+        int stride = 1;
+        for (; stride * 4 <= N; stride *= 4) x = m_cc->EvalRotateFoldMany(x, stride, 4);
+        if (stride < N) x = m_cc->EvalRotateFoldMany(x, stride, 2);
+        return x;
+    }
+
+    // The selection of several columns by ONE rank (ORDER BY key LIMIT k over
+    // rows).  As in placeMany the indicator depends on the rank
+    // and the target list alone: per batch tgt, z, the doubled-sinc PS and its
+    // level adjustment run once, exactly as in selectRanks (same memo tags,
+    // same target-list id, no masks of its own), and the linear tail runs per
+    // column -- the in-partition folds of all columns by EvalRotateFoldMany,
+    // the move's giant-step sums by EvalMultAddPlainCols (shared masks).
+    // Column c of the result holds the residues of selectRanks(ctx_Rank,
+    // cols[c], targets).
+    std::vector<Ciphertext<DCRTPoly>> selectRanksMany(const Ciphertext<DCRTPoly>& ctx_Rank,
+                                                      const std::vector<Ciphertext<DCRTPoly>>& cols,
+                                                      const std::vector<int>& targets) {
+        if (cols.empty()) throw OpenFHEException("selectRanksMany: no columns");
+        for (const auto& c : cols)
+            if (c->GetLevel() != cols[0]->GetLevel())
+                throw OpenFHEException("selectRanksMany: the columns must be at one level");
+        const int ps = selectCheck(ctx_Rank, targets);
+        const int K = (int)targets.size();
+        const size_t C = cols.size();
+        const sfhe::RankLayout L(N, max_batch);
+        sfhe::PhaseTimer ph(m_cc);
+        int Psel = 1;
+        while (Psel < K && Psel < L.P) Psel *= 2;
+        const int S = N * Psel, Bsel = (K + Psel - 1) / Psel;
+        const int np = 1 << (sfhe::ilog2(Psel) / 2);
+        const int tid = targetListId(targets);
+        auto rankS = ctx_Rank->Clone();
+        rankS->SetSlots(S);
+        std::vector<Ciphertext<DCRTPoly>> inputs(C);
+        for (size_t c = 0; c < C; ++c) {
+            inputs[c] = cols[c]->Clone();
+            inputs[c]->SetSlots(S);
+        }
+        const bool rebase = sfhe::sincRebase();
+        const auto& sincCoeffs = rebase ? sfhe::rebasedChebyshev(selectDoubledSincCoefficients<N>(), -1.0, 0.5)
+                                        : selectDoubledSincCoefficients<N>();
+        const double zmul = rebase ? 4.0 / 3.0 : 1.0, zadd = rebase ? 1.0 / 3.0 : 0.0;
+        std::vector<std::vector<Ciphertext<DCRTPoly>>> parts(C, std::vector<Ciphertext<DCRTPoly>>(Bsel));
+        const sfhe::BatchSplit split(m_cc, Bsel);
+        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
+        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());
+        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
+            const int b = split.mine[i];
+            Plaintext tgt = maskMemo({13, b, tid, (int)rankS->GetLevel(), S}, [&](auto& v) {
+                std::vector<double> T(S);
+                for (int p = 0; p < Psel; ++p) {
+                    const int k = b * Psel + p;
+                    std::fill(T.begin() + (size_t)p * N, T.begin() + (size_t)(p + 1) * N,
+                              (double)targets[k < K ? k : b * Psel]);
+                }
+                v.push_back(m_cc->MakeCKKSPackedPlaintext(T, 1, rankS->GetLevel(), nullptr, S));
+            })[0];
+            auto z = m_cc->EvalMult(m_cc->EvalSub(tgt, rankS), zmul / N / 2);
+            if (rebase) z = m_cc->EvalAdd(z, zadd);
+            ph.mark("  select batch: z");
+            auto hit = m_cc->EvalChebyshevSeriesPS(z, sincCoeffs, -1, 1);
+            const uint32_t psLevel = z->GetLevel() + (uint32_t)ps;
+            if (hit->GetLevel() < psLevel) hit = m_cc->AdjustLevel(hit, psLevel);
+            ph.mark("  select batch: sinc PS (shared)");
+            std::vector<Ciphertext<DCRTPoly>> masked(C);
+            for (size_t c = 0; c < C; ++c) masked[c] = m_cc->EvalMult(hit, inputs[c]);
+            const auto summed = foldPartitionsMany(masked);
+            ph.mark("  select batch: masks + in-partition folds");
+            std::vector<int> amounts(np);
+            for (int j = 0; j < np; ++j) amounts[j] = j;
+            std::vector<std::vector<Ciphertext<DCRTPoly>>> pre(C);
+            for (size_t c = 0; c < C; ++c) pre[c] = rot.rotateMany(summed[c], amounts);
+            std::vector<std::array<int, 5>> keys;
+            std::vector<int> steps;
+            for (int g = 0; g < Psel / np; ++g) {
+                keys.push_back({14, tid, b * 1024 + g, (int)pre[0][0]->GetLevel(), S});
+                steps.push_back(g * np);
+            }
+            const auto masks = maskMemoMany(keys, np, [&](size_t g, int j) {
+                std::vector<double> m(S, 0.0);
+                const int p = Psel - 1 - (np * (int)g + j);
+                if (b * Psel + p < K) m[(size_t)p * N] = 1.0;
+                return m_cc->MakeCKKSPackedPlaintext(vectorRotate(m, j), 1, pre[0][j]->GetLevel(), nullptr, S);
+            });
+            const auto giants = m_cc->EvalMultAddPlainCols(pre, masks);
+            const int base = (N + 1 - (b + 1) * Psel) % S;
+            for (size_t c = 0; c < C; ++c) {
+                for (const auto& gct : giants[c]) gct->SetSlots(S);
+                parts[c][b] = rot.rotate(rot.rotateSum(giants[c], steps), base);
+            }
+            ph.mark("  select batch: moves");
+        });
+        m_cc->JoinLanes();
+        m_cc->NoteSelection(split.mine.size());
+        m_cc->NoteSelectionColumns(C);
+        std::vector<Ciphertext<DCRTPoly>> outputs(C);
+        for (size_t c = 0; c < C; ++c) {
+            split.gatherParts(m_cc, parts[c]);
+            auto output = this->getZero()->Clone();
+            output->SetSlots(S);
+            for (int b = 0; b < Bsel; ++b) m_cc->EvalAddInPlace(output, parts[c][b]);
+            for (int sft = S / 2; sft >= N; sft /= 2) m_cc->EvalAddInPlace(output, rot.rotate(output, sft));
+            output->SetSlots(N);
+            outputs[c] = output;
+        }
+        ph.mark("select: batch sums + folds");
+        return outputs;
+    }
+
+    // ORDER BY key LIMIT k over rows: the (stable) rank of `keys`, then
+    // selectRanksMany of {keys, cols...}: first the selected keys, then the
+    // selected columns.
+    std::vector<Ciphertext<DCRTPoly>> selectRecords(const Ciphertext<DCRTPoly>& keys,
+                                                    const std::vector<Ciphertext<DCRTPoly>>& cols,
+                                                    const std::vector<int>& targets, SignFunc SignFunc,
+                                                    SignConfig& Cfg, bool stable) {
+        auto rank = stable ? constructRankStable(keys, SignFunc, Cfg) : constructRank(keys, SignFunc, Cfg);
+        std::vector<Ciphertext<DCRTPoly>> in{keys};
+        in.insert(in.end(), cols.begin(), cols.end());
+        return selectRanksMany(rank, in, targets);
     }
 
     // ---- hybrid placement I (reference :815-891,

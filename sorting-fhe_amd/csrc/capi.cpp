@@ -106,6 +106,10 @@ struct SorterBase {
     virtual size_t recordsGraphNodes() const = 0;
     virtual Ct selectRanks(const Ct& rank, const Ct& in, const std::vector<int>& targets) = 0;
     virtual Ct select(const Ct& in, const std::vector<int>& targets, SignConfig& cfg, bool stable) = 0;
+    virtual std::vector<Ct> selectRanksMany(const Ct& rank, const std::vector<Ct>& cols,
+                                            const std::vector<int>& targets) = 0;
+    virtual std::vector<Ct> selectRecords(const Ct& keys, const std::vector<Ct>& cols, const std::vector<int>& targets,
+                                          SignConfig& cfg, bool stable) = 0;
     virtual Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) = 0;
     virtual Ct hybrid(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk, int variant) = 0;
     virtual Ct place2N(const Ct& rank, const Ct& in) = 0;
@@ -151,6 +155,14 @@ struct Sorter : SorterBase {
     }
     Ct select(const Ct& in, const std::vector<int>& targets, SignConfig& cfg, bool stable) override {
         return ds.select(in, targets, SignFunc::CompositeSign, cfg, stable);
+    }
+    std::vector<Ct> selectRanksMany(const Ct& r, const std::vector<Ct>& cols,
+                                    const std::vector<int>& targets) override {
+        return ds.selectRanksMany(r, cols, targets);
+    }
+    std::vector<Ct> selectRecords(const Ct& keys, const std::vector<Ct>& cols, const std::vector<int>& targets,
+                                  SignConfig& cfg, bool stable) override {
+        return ds.selectRecords(keys, cols, targets, SignFunc::CompositeSign, cfg, stable);
     }
     Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) override {
         return ds.sort_hybrid1(in, SignFunc::CompositeSign, cfg, sk);
@@ -412,6 +424,15 @@ int sfhe_select_counts(sfhe_ctx* c, uint64_t* batches, uint64_t* fold_fused, uin
     return SFHE_OK;
 }
 
+int sfhe_select_cols_counts(sfhe_ctx* c, uint64_t* columns, uint64_t* fused, uint64_t* composed) {
+    REQUIRE(c && columns && fused && composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *columns = s.select_columns;
+    *fused = s.fold_cols_fused;
+    *composed = s.fold_cols_composed;
+    return SFHE_OK;
+}
+
 int sfhe_const_term_counts(sfhe_ctx* c, uint64_t* merged, uint64_t* single, uint64_t* composed) {
     REQUIRE(c && merged && single && composed, "null argument");
     auto s = c->cc->GetOpStats();
@@ -493,6 +514,19 @@ int sfhe_eval_rotate_fold(sfhe_ctx* c, const sfhe_ct* a, int32_t stride, uint32_
     REQUIRE(c && a && out, "null argument");
     REQUIRE(count >= 2 && count <= 8, "count must be in [2, 8]");
     return guard([&] { *out = wrap(c->cc->EvalRotateFold(a->ct, stride, count)); });
+}
+int sfhe_eval_rotate_fold_many(sfhe_ctx* c, const sfhe_ct* const* cts, size_t ncts, int32_t stride, uint32_t count,
+                               sfhe_ct** outs) {
+    REQUIRE(c && cts && outs, "null argument");
+    REQUIRE(ncts >= 1, "no ciphertexts");
+    for (size_t i = 0; i < ncts; ++i) REQUIRE(cts[i], "null ciphertext");
+    REQUIRE(count >= 2 && count <= 8, "count must be in [2, 8]");
+    return guard([&] {
+        std::vector<Ct> in;
+        for (size_t i = 0; i < ncts; ++i) in.push_back(cts[i]->ct);
+        auto folded = c->cc->EvalRotateFoldMany(in, stride, count);
+        for (size_t i = 0; i < ncts; ++i) outs[i] = wrap(folded[i]);
+    });
 }
 int sfhe_bootstrap_setup(sfhe_ctx* c, uint32_t budget_c2s, uint32_t budget_s2c, uint32_t slots) {
     REQUIRE(c, "null argument");
@@ -700,6 +734,39 @@ int sfhe_sorter_select(sfhe_sorter* s, const sfhe_ct* in, const uint32_t* target
     return guard([&] {
         auto cfg = cfgOf(n, dg, df);
         *out = wrap(s->impl->select(in->ct, t, cfg, stable != 0));
+    });
+}
+
+int sfhe_sorter_select_many(sfhe_sorter* s, const sfhe_ct* rank, const sfhe_ct* const* cols, size_t ncols,
+                            const uint32_t* targets, size_t count, sfhe_ct** outs) {
+    REQUIRE(s && rank && cols && targets && outs, "null argument");
+    REQUIRE(ncols >= 1 && ncols <= SFHE_MAX_COLUMNS, "column count out of range (1 .. SFHE_MAX_COLUMNS)");
+    for (size_t i = 0; i < ncols; ++i) REQUIRE(cols[i], "null column");
+    std::vector<int> t;
+    if (int rc = selectTargets(s, targets, count, s->impl->size(), &t)) return rc;
+    return guard([&] {
+        std::vector<Ct> in;
+        for (size_t i = 0; i < ncols; ++i) in.push_back(cols[i]->ct);
+        auto got = s->impl->selectRanksMany(rank->ct, in, t);
+        for (size_t i = 0; i < ncols; ++i) outs[i] = wrap(got[i]);
+    });
+}
+
+int sfhe_sorter_select_records(sfhe_sorter* s, const sfhe_ct* keys, const sfhe_ct* const* cols, size_t ncols,
+                               const uint32_t* targets, size_t count, int stable, int n, int dg, int df,
+                               sfhe_ct** keys_out, sfhe_ct** outs) {
+    REQUIRE(s && keys && targets && keys_out && (ncols == 0 || (cols && outs)), "null argument");
+    REQUIRE(ncols <= SFHE_MAX_COLUMNS, "column count out of range (0 .. SFHE_MAX_COLUMNS)");
+    for (size_t i = 0; i < ncols; ++i) REQUIRE(cols[i], "null column");
+    std::vector<int> t;
+    if (int rc = selectTargets(s, targets, count, s->impl->size(), &t)) return rc;
+    return guard([&] {
+        auto cfg = cfgOf(n, dg, df);
+        std::vector<Ct> in;
+        for (size_t i = 0; i < ncols; ++i) in.push_back(cols[i]->ct);
+        auto got = s->impl->selectRecords(keys->ct, in, t, cfg, stable != 0);
+        *keys_out = wrap(got[0]);
+        for (size_t i = 0; i < ncols; ++i) outs[i] = wrap(got[i + 1]);
     });
 }
 

@@ -3812,63 +3812,86 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalRotateSum(const std::vecto
 // launch; composed: per term sfp_automorph of the digits, then sfp_ks_inner
 // (first) / sfp_ks_inner_acc.  Both leave the canonical residue of the same
 // integer sum in acc, so everything after it is identical.
+// EvalRotateFold's terms: the Galois elements of the rotating ones (each with
+// its key present) and the number of identity terms.
+struct FoldTerms {
+    std::vector<uint32_t> gals;
+    uint32_t ident = 0;
+};
+static FoldTerms foldTerms(CryptoContextImpl<DCRTPoly>* cc, SfheContextState* s, uint32_t ctSlots, int32_t stride,
+                           uint32_t count) {
+    if (count < 2 || count > 8) SFHE_THROW("EvalRotateFold: count must be in [2, 8], got " + std::to_string(count));
+    const int64_t slots = ctSlots ? (int64_t)ctSlots : (int64_t)s->n / 2;
+    FoldTerms t;
+    for (uint32_t k = 0; k < count; ++k) {
+        // (the packing is `slots`-periodic: an amount acts as its residue modulo the slot count)
+        const int64_t r = (((int64_t)k * stride) % slots + slots) % slots;
+        if (r == 0 || cc->GaloisForRotation((int32_t)r) == 1) {
+            ++t.ident;
+            continue;
+        }
+        const uint32_t gal = cc->GaloisForRotation((int32_t)r);
+        if (!s->rotKeys.count(gal))
+            SFHE_THROW("EvalRotateFold: EvalKey for rotation " + std::to_string(r) + " is not found");
+        t.gals.push_back(gal);
+    }
+    return t;
+}
+
+// The terms' keys of the digits' special-prime tier (EvalFastRotation's rule)
+// for digits of `preStride` words at `ell` limbs; *tier is their (one) tier.
+static std::vector<const DeviceBufferPtr*> foldKeys(SfheContextState* s, const std::vector<uint32_t>& gals,
+                                                    uint32_t ell, size_t preStride, bool shard, int* tier) {
+    std::vector<const DeviceBufferPtr*> keys;
+    for (uint32_t gal : gals) {
+        const DeviceBufferPtr* key = s->rotFor(gal, ell);
+        if (!shard && (size_t)(ell + s->Kof((*key)->ksTier)) * s->n != preStride) key = &s->rotKeys.at(gal);
+        keys.push_back(key);
+    }
+    *tier = (*keys[0])->ksTier;
+    for (auto* k : keys)
+        if ((*k)->ksTier != *tier) SFHE_THROW("internal: rotation keys of different special-prime tiers");
+    if (!shard && preStride != (size_t)(ell + s->Kof(*tier)) * s->n)
+        SFHE_THROW("internal: extended digits of another special-prime tier");
+    return keys;
+}
+
+// c0' = sum_k sigma_k(c0): one permutation per term, summed by one weighted sum (weights 1)
+static void foldC0(SfheContextState* s, uint64_t* out0, const uint64_t* c0, const std::vector<uint32_t>& gals,
+                   uint32_t ell) {
+    std::vector<DeviceBufferPtr> c0s;
+    for (size_t k = 0; k < gals.size(); ++k) {
+        if (k) c0s.push_back(s->alloc((size_t)s->rows(ell) * s->n));
+        sfp_automorph(s->dev, k ? c0s.back()->ptr : out0, c0, gals[k], s->qmap(ell));
+    }
+    if (!c0s.empty()) {
+        std::vector<const uint64_t*> ins{out0};
+        for (auto& b : c0s) ins.push_back(b->ptr);
+        const std::vector<uint64_t> ones(ins.size() * s->rows(ell), 1);
+        sfp_lin_wsum(s->dev, out0, ins.data(), ones.data(), (uint32_t)ins.size(), s->qmap(ell));
+    }
+}
+
 Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalRotateFold(const Ciphertext<DCRTPoly>& a, int32_t stride,
                                                                  uint32_t count) {
     OpLock g(st.get());
     SfheContextState* s = st.get();
     if (!a) SFHE_THROW("EvalRotateFold: null ciphertext");
-    if (count < 2 || count > 8) SFHE_THROW("EvalRotateFold: count must be in [2, 8], got " + std::to_string(count));
+    const FoldTerms terms = foldTerms(this, s, a->slots, stride, count);
     SfheInternal::deps(s, {&a});  // (canonical rows: a pending product is rescaled first)
-    const int64_t slots = a->slots ? (int64_t)a->slots : (int64_t)s->n / 2;
-    std::vector<int32_t> amounts;
-    std::vector<uint32_t> gals;
-    uint32_t ident = 0;
-    for (uint32_t k = 0; k < count; ++k) {
-        // (the packing is `slots`-periodic: an amount acts as its residue modulo the slot count)
-        const int64_t r = (((int64_t)k * stride) % slots + slots) % slots;
-        if (r == 0 || GaloisForRotation((int32_t)r) == 1) {
-            ++ident;
-            continue;
-        }
-        const uint32_t gal = GaloisForRotation((int32_t)r);
-        if (!s->rotKeys.count(gal))
-            SFHE_THROW("EvalRotateFold: EvalKey for rotation " + std::to_string(r) + " is not found");
-        amounts.push_back((int32_t)r);
-        gals.push_back(gal);
-    }
+    const std::vector<uint32_t>& gals = terms.gals;
     Ciphertext<DCRTPoly> res;
     if (!gals.empty()) {
         const uint32_t R = (uint32_t)gals.size();
         const uint32_t level = a->level, ell = SfheInternal::ctEll(s, *a), n = s->n;
         auto pre = EvalFastRotationPrecompute(a);
         const bool shard = s->shardAt(ell);
-        // the terms' keys of the digits' special-prime tier (EvalFastRotation's rule)
-        std::vector<const DeviceBufferPtr*> keys;
-        for (uint32_t gal : gals) {
-            const DeviceBufferPtr* key = s->rotFor(gal, ell);
-            if (!shard && (size_t)(ell + s->Kof((*key)->ksTier)) * n != pre->stride) key = &s->rotKeys.at(gal);
-            keys.push_back(key);
-        }
-        const int tier = (*keys[0])->ksTier;
-        for (auto* k : keys)
-            if ((*k)->ksTier != tier) SFHE_THROW("internal: rotation keys of different special-prime tiers");
+        int tier = 0;
+        const auto keys = foldKeys(s, gals, ell, pre->stride, shard, &tier);
         const uint32_t K = s->Kof(tier), beta = pre->beta;
         const size_t stride_ = pre->stride;
-        if (!shard && stride_ != (size_t)(ell + K) * n)
-            SFHE_THROW("internal: extended digits of another special-prime tier");
         auto out = SfheInternal::newCt(this, level, a->slots);
-        // c0' = sum_k sigma_k(c0): one permutation per term, summed by one weighted sum (weights 1)
-        std::vector<DeviceBufferPtr> c0s;
-        for (uint32_t k = 0; k < R; ++k) {
-            if (k) c0s.push_back(s->alloc((size_t)s->rows(ell) * n));
-            sfp_automorph(s->dev, k ? c0s.back()->ptr : out->c0, a->c0, gals[k], st->qmap(ell));
-        }
-        if (!c0s.empty()) {
-            std::vector<const uint64_t*> ins{out->c0};
-            for (auto& b : c0s) ins.push_back(b->ptr);
-            const std::vector<uint64_t> ones(ins.size() * s->rows(ell), 1);
-            sfp_lin_wsum(s->dev, out->c0, ins.data(), ones.data(), (uint32_t)ins.size(), st->qmap(ell));
-        }
+        foldC0(s, out->c0, a->c0, gals, ell);
         auto acc = s->alloc(2 * stride_);
         s->dep(pre->ext.get());
         const char* knob = std::getenv("SFHE_SELECT_FOLD");  // (read per call: tests switch it)
@@ -3905,11 +3928,79 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalRotateFold(const Ciphertex
         s->countBytes((3.0 * ell * R + (2.0 * R + 1.0) * beta * (stride_ / n)) * n * 8);
         res = SfheInternal::traced(this, out, "EvalRotateFold");
     }
-    for (uint32_t k = 0; k < ident; ++k) res = res ? EvalAdd(res, a) : a->Clone();
+    for (uint32_t k = 0; k < terms.ident; ++k) res = res ? EvalAdd(res, a) : a->Clone();
+    return res;
+}
+
+// EvalRotateFold of several ciphertexts of one level: the terms, the keys and
+// the tier check are derived once; each column keeps its own ModUp, c0 sum and
+// ModDown; the columns' inner products are ONE sfp_ks_inner_aut_sum_cols call
+// (tiles of columns that read each key word once).  Where that prim is absent
+// (the C oracle), SFHE_SELECT_COLS=0, at a level dealt over ranks, where no
+// term rotates or where the prim declines, this is EvalRotateFold per column.
+std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalRotateFoldMany(
+    const std::vector<Ciphertext<DCRTPoly>>& a, int32_t stride, uint32_t count) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    if (a.empty()) SFHE_THROW("EvalRotateFoldMany: no columns");
+    for (const auto& c : a)
+        if (!c) SFHE_THROW("EvalRotateFoldMany: null ciphertext");
+    for (const auto& c : a)
+        if (c->level != a[0]->level || c->slots != a[0]->slots)
+            SFHE_THROW("EvalRotateFoldMany: the columns must be at one level");
+    const FoldTerms terms = foldTerms(this, s, a[0]->slots, stride, count);
+    const std::vector<uint32_t>& gals = terms.gals;
+    const size_t C = a.size();
+    const uint32_t R = (uint32_t)gals.size();
+    const uint32_t level = a[0]->level, ell = SfheInternal::ctEll(s, *a[0]), n = s->n;
+    const char* knob = std::getenv("SFHE_SELECT_COLS");  // (read per call: tests switch it)
+    std::vector<Ciphertext<DCRTPoly>> res(C);
+    int launches = -1;
+    if (sfp_ks_inner_aut_sum_cols && !(knob && *knob == '0') && !s->shardAt(ell) && R && C <= SFP_FOLD_COLS) {
+        for (const auto& c : a) SfheInternal::deps(s, {&c});
+        std::vector<std::shared_ptr<FastRotationPrecomp>> pre(C);
+        for (size_t c = 0; c < C; ++c) pre[c] = EvalFastRotationPrecompute(a[c]);
+        int tier = 0;
+        const auto keys = foldKeys(s, gals, ell, pre[0]->stride, false, &tier);
+        const uint32_t K = s->Kof(tier), beta = pre[0]->beta;
+        const size_t stride_ = pre[0]->stride;
+        std::vector<DeviceBufferPtr> acc(C);
+        std::vector<uint64_t*> a0(C), a1(C);
+        std::vector<const uint64_t*> ext(C), kp;
+        for (auto* k : keys) kp.push_back((*k)->ptr);
+        for (size_t c = 0; c < C; ++c) {
+            acc[c] = s->alloc(2 * stride_);
+            a0[c] = acc[c]->ptr;
+            a1[c] = acc[c]->ptr + stride_;
+            ext[c] = pre[c]->ext->ptr;
+            s->dep(pre[c]->ext.get());
+        }
+        launches = sfp_ks_inner_aut_sum_cols(s->dev, a0.data(), a1.data(), ext.data(), stride_, (uint32_t)C,
+                                             kp.data(), gals.data(), R, beta, ell, K, s->Lq);
+        for (size_t c = 0; c < C && launches > 0; ++c) {
+            auto out = SfheInternal::newCt(this, level, a[c]->slots);
+            foldC0(s, out->c0, a[c]->c0, gals, ell);
+            auto md = s->alloc((size_t)2 * ell * n);
+            sfp_moddown2(s->dev, out->c0, out->c1, acc[c]->ptr, stride_, ell, K, s->Lq, s->moddownConvOf(tier),
+                         s->pInvModQof(tier), 1, 0, md->ptr, 0);
+            s->stats.keyswitch += R;
+            s->stats.automorph += R;
+            s->countBytes((3.0 * ell * R + (2.0 * R + 1.0) * beta * (stride_ / n)) * n * 8);
+            res[c] = SfheInternal::traced(this, out, "EvalRotateFoldMany");
+            for (uint32_t k = 0; k < terms.ident; ++k) res[c] = EvalAdd(res[c], a[c]);
+        }
+    }
+    if (launches > 0) {
+        s->stats.fold_cols_fused += (uint64_t)launches;
+        return res;
+    }
+    for (size_t c = 0; c < C; ++c) res[c] = EvalRotateFold(a[c], stride, count);
+    s->stats.fold_cols_composed += C;
     return res;
 }
 
 void CryptoContextImpl<DCRTPoly>::NoteSelection(uint64_t batches) { st->stats.select_batches += batches; }
+void CryptoContextImpl<DCRTPoly>::NoteSelectionColumns(uint64_t columns) { st->stats.select_columns += columns; }
 
 // Double hoisting (Bossuat et al.'s hoisted ModDown): with acc_k the
 // extended-basis inner product of rotation k, p (.) ModDown(acc_k) and

@@ -465,8 +465,23 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     // (sfp_ks_inner / sfp_ks_inner_acc): the same residues.  OpStats
     // fold_fused / fold_composed count the calls of each kind.
     Ciphertext<DCRTPoly> EvalRotateFold(const Ciphertext<DCRTPoly>& a, int32_t stride, uint32_t count);
+    // Engine extension (a selection's payload columns): the
+    // results of EvalRotateFold(a[c], stride, count), residue for residue, for
+    // a non-empty list of ciphertexts at one level and slot count.  The terms,
+    // keys and tier check are derived once; each column keeps its ModUp, its
+    // sum of sigma_k(c0) and its ModDown; the columns' inner products are one
+    // prims.h sfp_ks_inner_aut_sum_cols call (tiles of columns that read each
+    // key word once).  Elsewhere (the C oracle, SFHE_SELECT_COLS=0 -- read per
+    // call --, a level whose rows are dealt over ranks, no rotating term, the
+    // prim declining) it is EvalRotateFold per column.  OpStats
+    // fold_cols_fused counts the prim's launches, fold_cols_composed the
+    // columns that went through EvalRotateFold.
+    std::vector<Ciphertext<DCRTPoly>> EvalRotateFoldMany(const std::vector<Ciphertext<DCRTPoly>>& a, int32_t stride,
+                                                         uint32_t count);
     // a selection ran `batches` indicator batches (OpStats)
     void NoteSelection(uint64_t batches);
+    // ... and served `columns` columns with them
+    void NoteSelectionColumns(uint64_t columns);
     // Engine extension (double hoisting): sum_t sum_k p_tk (.) EvalRotate(a_t, r_tk), then one
     // rescale -- EvalMultAddPlain over hoisted rotations.  Each input's rotations share one
     // ModUp; every key-switched term is multiplied by its plaintext in the extended basis Q*P
@@ -697,6 +712,9 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         // selections: indicator batches run; EvalRotateFold calls whose inner products were one
         // launch (sfp_ks_inner_aut_sum) / composed of the generic prims
         uint64_t select_batches = 0, fold_fused = 0, fold_composed = 0;
+        // multi-column selections: columns served; EvalRotateFoldMany's launches of
+        // sfp_ks_inner_aut_sum_cols / columns it passed to EvalRotateFold
+        uint64_t select_columns = 0, fold_cols_fused = 0, fold_cols_composed = 0;
     };
     OpStats GetOpStats() const;
     void ResetOpStats();
@@ -779,7 +797,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 10
+#define SFHE_FACADE_ABI_VERSION 11
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

@@ -3910,6 +3910,88 @@ __global__ __launch_bounds__(kThreads) void k_ks_inner_aut_sum(const KsFoldArgs 
     }
 }
 
+// k_ks_inner_aut_sum over a tile of CT columns (prims.h
+// sfp_ks_inner_aut_sum_cols; EvalRotateFoldMany): column c has its own
+// extended digits and accumulator pair, all columns share the R (Galois
+// element, key) pairs.  Per (k, j) the two source indices are computed and the
+// two key halves loaded (16 bytes each) ONCE for the tile; each column then
+// gathers its two digit words (8-byte loads, all issued before the step's
+// multiply-accumulates so the uncoalesced loads overlap) and does its four
+// maccs.  4 CT 128-bit accumulators, one reduction, 2 CT 16-byte stores.  The
+// accumulator bound is k_ks_inner_aut_sum's, per column.
+constexpr int kFoldTileMax = 4;
+constexpr uint32_t kFoldTileDefault = 2;  // (a measured tie with 4, fewer VGPRs; SFHE_SELECT_TILE selects the other)
+struct KsFoldColsArgs {
+    u64* acc0[kFoldTileMax];
+    u64* acc1[kFoldTileMax];
+    const u64* ext[kFoldTileMax];
+    size_t extStride;
+    const u64* key[SFP_FOLD_MAX];
+    uint32_t gal[SFP_FOLD_MAX];
+    uint32_t R, beta, ell, rows, Lq, keyRows;
+};
+static_assert(sizeof(KsFoldColsArgs) + sizeof(const sf_barrett*) + sizeof(uint32_t) <= 4096,
+              "k_ks_inner_aut_sum_cols: the arguments exceed the 4 KB kernel-argument block");
+static_assert(SF_MAX_PRIME_BITS * 2 + 8 <= 128,
+              "k_ks_inner_aut_sum_cols: 2^8 products of 2^120 must fit 128 bits");
+template <int CT>
+__global__ __launch_bounds__(kThreads) void k_ks_inner_aut_sum_cols(const KsFoldColsArgs A,
+                                                                    const sf_barrett* __restrict__ bar,
+                                                                    uint32_t logn) {
+    static_assert(CT >= 2 && CT <= kFoldTileMax, "tile width");
+    const size_t extStride = A.extStride;
+    const uint32_t R = A.R, beta = A.beta, ell = A.ell, NP = A.keyRows;
+    const size_t pairs = ((size_t)A.rows << logn) >> 1;
+    const uint32_t n = 1u << logn;
+    const u64 mask = 2ull * n - 1;
+    for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < pairs; i += (size_t)gridDim.x * kThreads) {
+        const size_t e = 2 * i;
+        const uint32_t t = (uint32_t)(e >> logn);
+        const uint32_t x = (uint32_t)(e & (n - 1));
+        const uint32_t kr = t < ell ? t : A.Lq + (t - ell);
+        const sf_barrett B = loadBar(bar, kr);
+        const size_t row = e - x;
+        const u64 b0 = 2ull * sf_brev(x, logn) + 1, b1 = 2ull * sf_brev(x + 1, logn) + 1;
+        Acc s0[CT], s0b[CT], s1[CT], s1b[CT];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) s0[c] = s0b[c] = s1[c] = s1b[c] = Acc{0, 0};
+        for (uint32_t k = 0; k < R; ++k) {
+            const u64 g = A.gal[k];
+            const size_t src0 = row + sf_brev((uint32_t)(((b0 * g & mask) - 1) >> 1), logn);
+            const size_t src1 = row + sf_brev((uint32_t)(((b1 * g & mask) - 1) >> 1), logn);
+            const u64* __restrict__ key = A.key[k];
+            for (uint32_t j = 0; j < beta; ++j) {
+                u64 ex[CT], ey[CT];
+#pragma unroll
+                for (int c = 0; c < CT; ++c) {
+                    ex[c] = A.ext[c][j * extStride + src0];
+                    ey[c] = A.ext[c][j * extStride + src1];
+                }
+                const u64* kb = key + (size_t)j * 2 * NP * n + ((size_t)kr << logn) + x;
+                const ulonglong2 b2 = *reinterpret_cast<const ulonglong2*>(kb);
+                const ulonglong2 a2 = *reinterpret_cast<const ulonglong2*>(kb + (size_t)NP * n);
+#pragma unroll
+                for (int c = 0; c < CT; ++c) {
+                    macc(s0[c], ex[c], b2.x);
+                    macc(s0b[c], ey[c], b2.y);
+                    macc(s1[c], ex[c], a2.x);
+                    macc(s1b[c], ey[c], a2.y);
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            ulonglong2 o0, o1;
+            o0.x = sf_reduce128_acc(s0[c].lo, s0[c].hi, &B);
+            o0.y = sf_reduce128_acc(s0b[c].lo, s0b[c].hi, &B);
+            o1.x = sf_reduce128_acc(s1[c].lo, s1[c].hi, &B);
+            o1.y = sf_reduce128_acc(s1b[c].lo, s1b[c].hi, &B);
+            *reinterpret_cast<ulonglong2*>(A.acc0[c] + e) = o0;
+            *reinterpret_cast<ulonglong2*>(A.acc1[c] + e) = o1;
+        }
+    }
+}
+
 // ============================================================================
 // sampling / loading
 
@@ -6597,6 +6679,89 @@ int sfp_ks_inner_aut_sum(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint6
     });
     checkLaunch(d, "ks_inner_aut_sum");
     return 0;
+}
+
+int sfp_ks_inner_aut_sum_cols(sfp_dev* d, uint64_t* const* acc0, uint64_t* const* acc1, const uint64_t* const* ext,
+                              size_t extStride, uint32_t nc, const uint64_t* const* keys, const uint32_t* gals,
+                              uint32_t R, uint32_t beta, uint32_t ell, uint32_t K, uint32_t Lq) {
+    // declined (nothing done): sfp_ks_inner_aut_sum's cases for any column, a
+    // column count the prim does not take, an output overlapping an input or
+    // another output
+    if (!nc || nc > SFP_FOLD_COLS) return -1;
+    if (!R || R > SFP_FOLD_MAX || !beta || R * beta > kFoldMaxProducts || d->kg.rows || d->n < 2) return -1;
+    if (!ell || ell > Lq || ell + K > SFP_MAX_LIMBS || Lq + K > d->np || extStride < (size_t)(ell + K) * d->n)
+        return -1;
+    const size_t total = (size_t)(ell + K) * d->n;
+    uintptr_t bits = (uintptr_t)(extStride * 8);
+    struct Span {
+        uintptr_t lo, hi;
+    };
+    std::vector<Span> in, out;
+    for (uint32_t k = 0; k < R; ++k) {
+        if (!keys[k] || !(gals[k] & 1) || gals[k] >= 2 * d->n) return -1;
+        bits |= (uintptr_t)keys[k];
+        in.push_back({(uintptr_t)keys[k], (uintptr_t)(keys[k] + (size_t)beta * 2 * (Lq + K) * d->n)});
+    }
+    for (uint32_t c = 0; c < nc; ++c) {
+        if (!acc0[c] || !acc1[c] || !ext[c]) return -1;
+        bits |= (uintptr_t)acc0[c] | (uintptr_t)acc1[c] | (uintptr_t)ext[c];
+        in.push_back({(uintptr_t)ext[c], (uintptr_t)(ext[c] + (size_t)(beta - 1) * extStride + total)});
+        out.push_back({(uintptr_t)acc0[c], (uintptr_t)(acc0[c] + total)});
+        out.push_back({(uintptr_t)acc1[c], (uintptr_t)(acc1[c] + total)});
+    }
+    if (bits & 15) return -1;
+    for (size_t o = 0; o < out.size(); ++o) {
+        for (const Span& s : in)
+            if (out[o].lo < s.hi && s.lo < out[o].hi) return -1;
+        for (size_t p = 0; p < o; ++p)
+            if (out[o].lo < out[p].hi && out[p].lo < out[o].hi) return -1;
+    }
+    // tiles of the default width; a remainder of 2 or 3 as a 2-tile (+ 1), a
+    // remainder of 1 as the one-column prim.  SFHE_SELECT_TILE=2|4 selects the
+    // other width (A/B; read per call)
+    const char* tv = std::getenv("SFHE_SELECT_TILE");
+    const uint32_t wide = tv && (tv[0] == '2' || tv[0] == '4') ? (uint32_t)(tv[0] - '0') : kFoldTileDefault;
+    int launches = 0;
+    for (uint32_t c0 = 0; c0 < nc;) {
+        const uint32_t left = nc - c0, CT = left >= wide ? wide : left >= 2 ? 2 : 1;
+        if (CT == 1) {
+            if (sfp_ks_inner_aut_sum(d, acc0[c0], acc1[c0], ext[c0], extStride, keys, gals, R, beta, ell, K, Lq))
+                record(d, "ks_inner_aut_sum_cols (the one-column prim declined a checked shape)",
+                       hipErrorInvalidValue);
+            c0 += 1;
+            ++launches;
+            continue;
+        }
+        KsFoldColsArgs a;
+        std::memset(&a, 0, sizeof a);
+        for (uint32_t c = 0; c < CT; ++c) {
+            a.acc0[c] = acc0[c0 + c];
+            a.acc1[c] = acc1[c0 + c];
+            a.ext[c] = ext[c0 + c];
+        }
+        a.extStride = extStride;
+        for (uint32_t k = 0; k < R; ++k) {
+            a.key[k] = keys[k];
+            a.gal[k] = gals[k];
+        }
+        a.R = R;
+        a.beta = beta;
+        a.ell = ell;
+        a.rows = ell + K;
+        a.Lq = Lq;
+        a.keyRows = Lq + K;
+        // per limb: CT * R * beta gathered ext words, 2 * R * beta key rows once for the tile, 2 CT rows written
+        timedLaunch(d, SFP_FAM_KSINNER, 8.0 * total * ((CT + 2.0) * R * beta + 2.0 * CT), [&] {
+            if (CT == 4)
+                SFP_GO(k_ks_inner_aut_sum_cols<4>, dim3(ewGrid(total / 2)), dim3(kThreads), a, d->bar, d->logn);
+            else
+                SFP_GO(k_ks_inner_aut_sum_cols<2>, dim3(ewGrid(total / 2)), dim3(kThreads), a, d->bar, d->logn);
+        });
+        checkLaunch(d, "ks_inner_aut_sum_cols");
+        c0 += CT;
+        ++launches;
+    }
+    return launches;
 }
 
 void sfp_ks_inner_mul(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_t* ext, size_t extStride,

@@ -413,6 +413,29 @@ SFP_OPTIONAL int sfp_ks_inner_aut_sum(sfp_dev* d, uint64_t* acc0, uint64_t* acc1
                                       size_t ext_stride, const uint64_t* const* keys, const uint32_t* gals,
                                       uint32_t R, uint32_t beta, uint32_t ell, uint32_t K, uint32_t Lq);
 
+// ---- optional: sfp_ks_inner_aut_sum over several columns that share the keys ----
+// for c < nc: acc_c,p = sum_k sum_j sigma_k(ext_c,j) (.) key_k,p,j  (k < R, j < beta)
+// nc columns (1 <= nc <= SFP_FOLD_COLS: the payload columns of a selection,
+// EvalRotateFoldMany), each with its own extended digits ext[c] (one stride)
+// and accumulator pair acc0[c] / acc1[c], share the R <= SFP_FOLD_MAX (Galois
+// element, key) pairs.  Issued as tiles of columns: a tile reads each key word
+// and computes each source index once for its columns (the keys are two
+// thirds of the one-column prim's traffic); a single left-over column runs
+// sfp_ks_inner_aut_sum.  Column c's output is the canonical residue of the
+// integer sum sfp_ks_inner_aut_sum leaves for it.  Every array is a host array
+// that travels in the kernels' arguments: no upload and no host
+// synchronisation, any lane.  Returns the number of launches issued (>= 1),
+// or -1 with nothing done: nc = 0 or nc > SFP_FOLD_COLS, R > SFP_FOLD_MAX,
+// R * beta > 256, a row not 16-byte aligned, a sliced key geometry, an output
+// overlapping an input or another output.  Weak like the prims above: where
+// its address is null (the C oracle) or it declines, the host layer runs the
+// composed form.
+#define SFP_FOLD_COLS 16
+SFP_OPTIONAL int sfp_ks_inner_aut_sum_cols(sfp_dev* d, uint64_t* const* acc0, uint64_t* const* acc1,
+                                           const uint64_t* const* ext, size_t ext_stride, uint32_t nc,
+                                           const uint64_t* const* keys, const uint32_t* gals, uint32_t R,
+                                           uint32_t beta, uint32_t ell, uint32_t K, uint32_t Lq);
+
 // ---- optional: CKKS decoding on the device (the end of a decryption) ----------
 // `count` row sets src + b * srcStride, each nl (1 or 2) COEFFICIENT-domain
 // rows of n words modulo primes 0 .. nl-1 (c0 + c1 s after its inverse NTT),

@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "sfhe_sorter_place_many", "sfhe_sorter_sort_records", "sfhe_sorter_records_graph_nodes", "sfhe_place_counts",
     "sfhe_select_params", "sfhe_sorter_select_ranked", "sfhe_sorter_select", "sfhe_eval_rotate_fold",
     "sfhe_select_counts",
+    "sfhe_sorter_select_many", "sfhe_sorter_select_records", "sfhe_eval_rotate_fold_many", "sfhe_select_cols_counts",
 ]
 
 MAX_COLUMNS = 8  # SFHE_MAX_COLUMNS
@@ -192,6 +193,11 @@ _SIGS = {
     "sfhe_sorter_select": (C.c_int, [_VP, _VP, _PU32, _SZ, C.c_int, C.c_int, C.c_int, C.c_int, _PVP]),
     "sfhe_eval_rotate_fold": (C.c_int, [_VP, _VP, C.c_int32, _U32, _PVP]),
     "sfhe_select_counts": (C.c_int, [_VP, _PU64, _PU64, _PU64]),
+    "sfhe_sorter_select_many": (C.c_int, [_VP, _VP, _PVP, _SZ, _PU32, _SZ, _PVP]),
+    "sfhe_sorter_select_records": (C.c_int, [_VP, _VP, _PVP, _SZ, _PU32, _SZ, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             _PVP, _PVP]),
+    "sfhe_eval_rotate_fold_many": (C.c_int, [_VP, _PVP, _SZ, C.c_int32, _U32, _PVP]),
+    "sfhe_select_cols_counts": (C.c_int, [_VP, _PU64, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -562,6 +568,24 @@ class Engine:
         self._chk(self.lib.sfhe_select_counts(self.ctx, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def rotate_fold_many(self, cts, stride: int, count: int) -> list:
+        """[rotate_fold(ct, stride, count) for ct in cts], the same residues, for ciphertexts at
+        one level and slot count: on the device the key inner products of all of them run as
+        tiles of columns that read each rotation key once (EvalRotateFoldMany)."""
+        cts = list(cts)
+        hs = (_VP * max(len(cts), 1))(*[c.h if c is not None else None for c in cts])
+        outs = (_VP * max(len(cts), 1))()
+        self._chk(self.lib.sfhe_eval_rotate_fold_many(self.ctx, hs, len(cts), int(stride), int(count), outs))
+        return [Ct(self, C.c_void_p(outs[k])) for k in range(len(cts))]
+
+    def select_cols_counts(self):
+        """(columns, fused, composed) since the last op_stats reset: columns the multi-column
+        selections served, rotate_fold_many's launches of the column-tiled kernel, columns it
+        passed to rotate_fold's path."""
+        v = [C.c_uint64() for _ in range(3)]
+        self._chk(self.lib.sfhe_select_cols_counts(self.ctx, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def bootstrap_setup(self, level_budget=(5, 5), slots: int = 0):
         """EvalBootstrapSetup + EvalBootstrapKeyGen for `slots`-slot ciphertexts."""
         self._chk(self.lib.sfhe_bootstrap_setup(self.ctx, level_budget[0], level_budget[1], slots))
@@ -723,6 +747,34 @@ class Sorter:
         """rank (stable: rank_stable, one level more) of ct, then select_ranked; always eager."""
         buf, k = self._targets(targets)
         return self.eng._new(self.eng.lib.sfhe_sorter_select, self.h, ct.h, buf, k, int(bool(stable)), n, dg, df)
+
+    def select_many(self, rank: Ct, cts, targets) -> list:
+        """select_ranked(rank, ct, targets) of every column with ONE indicator evaluation per
+        batch: the same residues as the separate calls.  Payload values must lie in [-1, 1]."""
+        cts = list(cts)
+        buf, k = self._targets(targets)
+        hs = (_VP * max(len(cts), 1))(*[c.h if c is not None else None for c in cts])
+        outs = (_VP * max(len(cts), 1))()
+        self.eng._chk(self.eng.lib.sfhe_sorter_select_many(self.h, rank.h, hs, len(cts), buf, k, outs))
+        return [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cts))]
+
+    def select_records(self, keys: Ct, cts=(), targets=(0,), stable: bool = True, n: int = 3, dg: int = 2,
+                       df: int = 2):
+        """ORDER BY key LIMIT k over rows: (select(keys, targets), [columns' rows in the same
+        order]); stable: equal keys keep their input order (one level more, as select)."""
+        cts = list(cts)
+        buf, k = self._targets(targets)
+        hs = (_VP * max(len(cts), 1))(*[c.h if c is not None else None for c in cts])
+        outs = (_VP * max(len(cts), 1))()
+        ko = C.c_void_p()
+        self.eng._chk(self.eng.lib.sfhe_sorter_select_records(self.h, keys.h, hs, len(cts), buf, k,
+                                                              int(bool(stable)), n, dg, df, C.byref(ko), outs))
+        return Ct(self.eng, ko), [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cts))]
+
+    def top_k_records(self, keys: Ct, cts, k: int, largest: bool = False, **kw):
+        """The rows of the k smallest keys in ascending key order (largest: the k largest, descending)."""
+        return self.select_records(keys, cts, [self.N - 1 - i for i in range(k)] if largest else list(range(k)),
+                                   **kw)
 
     def top_k(self, ct: Ct, k: int, largest: bool = False, **kw) -> Ct:
         """The k smallest values in ascending order (largest: the k largest, descending)."""
