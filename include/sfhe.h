@@ -35,7 +35,10 @@ extern "C" {
  * and the selection: sfhe_select_params, sfhe_sorter_select_ranked,
  * sfhe_sorter_select, sfhe_eval_rotate_fold, sfhe_select_counts, and the
  * record selection: sfhe_sorter_select_many, sfhe_sorter_select_records,
- * sfhe_eval_rotate_fold_many, sfhe_select_cols_counts) */
+ * sfhe_eval_rotate_fold_many, sfhe_select_cols_counts, and the ordering by
+ * several keys: SFHE_LEX_KEYS, sfhe_lex_sort_depth, sfhe_sorter_rank_lex,
+ * sfhe_sorter_sort_records_lex, sfhe_sorter_select_records_lex,
+ * sfhe_eval_lex_step, sfhe_lex_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -353,6 +356,44 @@ int sfhe_sorter_select_many(sfhe_sorter* s, const sfhe_ct* rank, const sfhe_ct* 
 int sfhe_sorter_select_records(sfhe_sorter* s, const sfhe_ct* keys, const sfhe_ct* const* cols, size_t ncols,
                                const uint32_t* targets, size_t count, int stable, int n, int dg, int df,
                                sfhe_ct** keys_out, sfhe_ct** outs);
+/* Engine extensions (additions at ABI 3): ordering by several keys -- ORDER BY
+ * a, b [DESC], ... over rows.  `keys` holds 1 <= nkeys <= SFHE_LEX_KEYS key
+ * columns at one level and slot count, keys[0] the most significant;
+ * descending[i] != 0 orders by key i descending (descending = NULL: every key
+ * ascending).  Rows equal on every key keep their input order.  Per key, two
+ * values must be equal or at least the sign configuration's resolution apart
+ * (1/N for the defaults).
+ * sfhe_lex_sort_depth: the mult_depth the record sort by nkeys keys needs, the
+ * stable sort's (sfhe_direct_sort_params' depth + 1 for the default
+ * configuration) + nkeys - 1.
+ * sfhe_sorter_rank_lex: the rank of every row in that order, nkeys - 1 levels
+ * below sfhe_sorter_rank_stable; with one ascending key exactly its residues.
+ * sfhe_sorter_sort_records_lex: that rank, then one placement of the keys and
+ * the ncols payload columns: keys_out[i] is key column i and outs[j] column j
+ * in sorted order.  sfhe_sorter_select_records_lex: that rank, then the rows of
+ * the target ranks (as sfhe_sorter_select_records; rotation keys from
+ * sfhe_select_params).  nkeys + ncols may be at most 1 + SFHE_MAX_COLUMNS.
+ * A key count or column count out of range or a NULL entry: SFHE_EINVAL; keys
+ * at different levels or too little depth: SFHE_ESCHEME, and the message
+ * names the depth needed.  Always eager. */
+#define SFHE_LEX_KEYS 4
+int sfhe_lex_sort_depth(uint32_t N, int n, int dg, int df, uint32_t nkeys, uint32_t* mult_depth);
+int sfhe_sorter_rank_lex(sfhe_sorter* s, const sfhe_ct* const* keys, size_t nkeys, const int* descending, int n,
+                         int dg, int df, sfhe_ct** out);
+int sfhe_sorter_sort_records_lex(sfhe_sorter* s, sfhe_ct* const* keys, size_t nkeys, const int* descending,
+                                 sfhe_ct* const* cols, size_t ncols, int n, int dg, int df, sfhe_ct** keys_out,
+                                 sfhe_ct** outs);
+int sfhe_sorter_select_records_lex(sfhe_sorter* s, const sfhe_ct* const* keys, size_t nkeys, const int* descending,
+                                   const sfhe_ct* const* cols, size_t ncols, const uint32_t* targets, size_t count,
+                                   int n, int dg, int df, sfhe_ct** keys_out, sfhe_ct** outs);
+/* v + (1 - q) (.) u, relinearised, one level below u (one relinearisation,
+ * one rescale): the lexicographic rank's Horner step.  v and q may have more
+ * limbs than u (a numerically lower level).  sfhe_lex_counts: such steps whose
+ * tensor ran as one fused launch (sfp_lex_tensor) and as the composed generic
+ * prims since the last sfhe_op_stats reset (SFHE_LEX_FUSED=0, read per call,
+ * composes; the results are bit-identical). */
+int sfhe_eval_lex_step(sfhe_ctx* c, const sfhe_ct* v, const sfhe_ct* q, const sfhe_ct* u, sfhe_ct** out);
+int sfhe_lex_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
 /* nodes of the captured record sort (0 while none); sfhe_sorter_graph_nodes
  * keeps reporting the plain / stable sort's graph */
 int sfhe_sorter_records_graph_nodes(const sfhe_sorter* s, uint64_t* nodes);

@@ -23,6 +23,9 @@
 // a key column + placeMany of the keys and their payload columns.
 // Record selection: selectRanksMany / selectRecords select the
 // rows of chosen ranks, likewise with one indicator per batch for all columns.
+// Several keys: constructRankLex ranks rows in (key_1, ...,
+// key_m, input index) order in one pass; sortRecordsLex / selectRecordsLex
+// place / select the keys and payload columns by it.
 //
 // Engine-specific scheduling (identical slot values, fewer key switches):
 //   * baby-step rotations of one ciphertext share one hoisted ModUp;
@@ -116,6 +119,11 @@ inline int directSortDepth(int N, const CompositeSignConfig& c) {
 //   rank: 1 (mask) + sign + 2 (tie term)
 inline int stableRankDepth(const CompositeSignConfig& c) { return 1 + compositeSignDepth(c) + 2; }
 inline int stableSortDepth(int N, const CompositeSignConfig& c) { return directSortDepth(N, c) + 1; }
+// The lexicographic sort by m keys: every key's tie term, then
+// one Horner step (EvalLexStep, one level) per key after the first.
+#define SFHE_LEX_KEYS 4
+inline int lexRankDepth(const CompositeSignConfig& c, int m) { return stableRankDepth(c) + (m - 1); }
+inline int lexSortDepth(int N, const CompositeSignConfig& c, int m) { return stableSortDepth(N, c) + (m - 1); }
 
 // getSizeParameters' (depth, rotation keys) for N (reference :87-201);
 // nullptr when the reference has no entry.
@@ -552,6 +560,109 @@ class DirectSort : public SortBase<N> {
         }
         // remove the self comparison: step(selfOffset) = 1 (reference: step(0) = 1/2)
         return m_cc->EvalSub(rank, offsetSelf ? 1.0 : 0.5);
+    }
+
+    // The lexicographic stable rank by m = keys.size() keys (1 <= m <=
+    // SFHE_LEX_KEYS), key i descending where descending[i]: the number of j
+    // before r in (key_1, ..., key_m, input index) order.  In
+    // constructRankStable's slot layout, with s_i the sign of key i's
+    // difference, v_i = s_i (.) (1/2 - w (.) s_i) its tie term and e_i = 1 -
+    // s_i^2 its "equal on this key",
+    //   t = (1/2 + w) + v_1 + e_1 (.) (v_2 + e_2 (.) (v_3 + ...)):
+    // where key 1 differs t = 1/2 + s_1/2, where it ties t is key 2's stable
+    // term, and so on down to the index.  Per batch: the m signs, the m tie
+    // terms (EvalTieTerm), q_i = s_i^2 for i < m in one EvalMultMany, then the
+    // Horner steps from the last key inwards (EvalLexStep, one level each):
+    // m - 1 levels below constructRankStable.  A descending key swaps the
+    // operands of its difference.  The self offset goes on the first key's
+    // difference only (+kSelfOffset whatever its direction), so s_1 = 1 and
+    // e_1 ~ 0 in the self slots and the constants are constructRankStable's.
+    // The masks, tie weights and base constants are that method's memo
+    // entries.  Precondition per key: two values are equal or at least the
+    // sign configuration's resolution apart.
+    Ciphertext<DCRTPoly> constructRankLex(const std::vector<Ciphertext<DCRTPoly>>& keys,
+                                          const std::vector<bool>& descending, SignFunc SignFunc, SignConfig& Cfg) {
+        const int m = (int)keys.size();
+        if (m < 1 || m > SFHE_LEX_KEYS)
+            throw OpenFHEException("lexicographic rank: " + std::to_string(m) + " keys (1 .. " +
+                                   std::to_string(SFHE_LEX_KEYS) + " are supported)");
+        if ((int)descending.size() != m)
+            throw OpenFHEException("lexicographic rank: one descending flag per key is needed");
+        for (const auto& k : keys)
+            if (k->GetLevel() != keys[0]->GetLevel() || k->GetSlots() != keys[0]->GetSlots())
+                throw OpenFHEException("lexicographic rank: the keys must be at one level and slot count");
+        const int need = (int)keys[0]->GetLevel() + sfhe::lexRankDepth(Cfg.compos, m);
+        if ((int)m_cc->GetMultiplicativeDepth() < need)
+            throw OpenFHEException("lexicographic rank: needs multiplicative depth " + std::to_string(need) +
+                                   " (the stable rank's, and one level per key after the first); the context has " +
+                                   std::to_string(m_cc->GetMultiplicativeDepth()));
+        if (m == 1 && !descending[0]) return constructRankMode(keys[0], SignFunc, Cfg, true);
+        const sfhe::RankLayout L(N, max_batch);
+        sfhe::PhaseTimer ph(m_cc);
+        std::vector<int> amounts(L.npRank);
+        for (int i = 0; i < L.npRank; ++i) amounts[i] = i;
+        std::vector<std::vector<Ciphertext<DCRTPoly>>> pre(m);
+        for (int k = 0; k < m; ++k) {
+            pre[k] = rot.rotateMany(keys[k], amounts);
+            for (auto& p : pre[k]) p->SetSlots(L.S);
+        }
+        ph.mark("lex rank: baby rotations");
+
+        auto rank = this->getZero()->Clone();
+        rank->SetSlots(L.S);
+        const bool offsetSelf = sfhe::selfOffset();
+        std::vector<Ciphertext<DCRTPoly>> parts(L.B);
+        const sfhe::BatchSplit split(m_cc, L.B);
+        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
+        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());
+        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
+            const int b = split.mine[i];
+            std::vector<Ciphertext<DCRTPoly>> s(m), v(m);
+            for (int k = 0; k < m; ++k) {
+                // minuend - subtrahend: x_r - x_j ascending, x_j - x_r descending
+                auto shifted = vecRotsOpt(pre[k], L.P, L.S, L.npRank, b);
+                auto dup = keys[k]->Clone();
+                dup->SetSlots(L.S);
+                auto minuend = descending[k] ? shifted : dup;
+                const auto& subtrahend = descending[k] ? dup : shifted;
+                if (k == 0 && b == 0 && offsetSelf) {
+                    const Plaintext& off = maskMemo({7, 0, 0, (int)dup->GetLevel(), L.S}, [&](auto& mv) {
+                        std::vector<double> o(L.S, 0.0);
+                        std::fill(o.begin(), o.begin() + N, sfhe::kSelfOffset);
+                        mv.push_back(m_cc->MakeCKKSPackedPlaintext(o, 1, dup->GetLevel(), nullptr, L.S));
+                    })[0];
+                    minuend = m_cc->EvalAdd(minuend, off);
+                }
+                s[k] = sign(m_cc->EvalSub(minuend, subtrahend), m_cc, SignFunc, Cfg);
+            }
+            ph.mark("  lex rank batch: vecRotsOpt + signs");
+            const Plaintext& W = maskMemo({11, b, 0, (int)s[0]->GetLevel(), L.S}, [&](auto& mv) {
+                mv.push_back(m_cc->MakeCKKSPackedPlaintext(generateTieWeights(L.S, L.P, b), 1, s[0]->GetLevel(),
+                                                           nullptr, L.S));
+            })[0];
+            for (int k = 0; k < m; ++k) v[k] = m_cc->EvalTieTerm(s[k], W, 0.5);
+            const std::vector<Ciphertext<DCRTPoly>> head(s.begin(), s.end() - 1);
+            const auto q = m_cc->EvalMultMany(head, head);
+            auto u = v[m - 1];
+            for (int k = m - 2; k >= 0; --k) u = m_cc->EvalLexStep(v[k], q[k], u);
+            parts[b] = u;
+            ph.mark("  lex rank batch: tie terms + Horner steps");
+        });
+        m_cc->JoinLanes();
+        split.gatherParts(m_cc, parts);
+        for (int b = 0; b < L.B; ++b) m_cc->EvalAddInPlace(rank, parts[b]);
+        ph.mark("lex rank: batches");
+        for (int sft = L.S / 2; sft >= N; sft /= 2) m_cc->EvalAddInPlace(rank, rot.rotate(rank, sft));
+        ph.mark("lex rank: folds");
+        rank->SetSlots(N);
+        // the terms' constants 1/2 + w, less the self comparison (constructRankMode)
+        const double self = 0.5 - (offsetSelf ? 1.0 : 0.5);
+        const Plaintext& base = maskMemo({12, offsetSelf ? 1 : 0, 0, (int)rank->GetLevel(), N}, [&](auto& mv) {
+            std::vector<double> c(N);
+            for (int r = 0; r < N; ++r) c[r] = r + self;
+            mv.push_back(m_cc->MakeCKKSPackedPlaintext(c, 1, rank->GetLevel(), nullptr, N));
+        })[0];
+        return m_cc->EvalAdd(rank, base);
     }
 
     // Rotates partition k = np*i + j of the masked inputs left by ib*P + k
@@ -1008,6 +1119,48 @@ class DirectSort : public SortBase<N> {
         std::vector<Ciphertext<DCRTPoly>> in{keys};
         in.insert(in.end(), cols.begin(), cols.end());
         return selectRanksMany(rank, in, targets);
+    }
+
+    // ---- records ordered by several keys (ORDER BY a, b [DESC]) ----
+    // The keys and payload columns of a lexicographic record sort / selection:
+    // {keys..., cols...}, as many columns as a one-key record call takes.
+    std::vector<Ciphertext<DCRTPoly>> lexColumns(const char* what, const std::vector<Ciphertext<DCRTPoly>>& keys,
+                                                 const std::vector<Ciphertext<DCRTPoly>>& cols, size_t maxCols) {
+        if (keys.size() + cols.size() > 1 + maxCols)
+            throw OpenFHEException(std::string(what) + ": " + std::to_string(keys.size()) + " keys and " +
+                                   std::to_string(cols.size()) + " payload columns (at most " +
+                                   std::to_string(1 + maxCols) + " columns in all)");
+        std::vector<Ciphertext<DCRTPoly>> in(keys);
+        in.insert(in.end(), cols.begin(), cols.end());
+        return in;
+    }
+    void lexDepthCheck(const char* what, const std::vector<Ciphertext<DCRTPoly>>& keys, SignConfig& Cfg) {
+        if (keys.empty()) return;  // (constructRankLex refuses)
+        const int need = (int)keys[0]->GetLevel() + sfhe::lexSortDepth(N, Cfg.compos, (int)keys.size());
+        if ((int)m_cc->GetMultiplicativeDepth() < need)
+            throw OpenFHEException(std::string(what) + ": needs multiplicative depth " + std::to_string(need) +
+                                   " (the stable sort's, and one level per key after the first); the context has " +
+                                   std::to_string(m_cc->GetMultiplicativeDepth()));
+    }
+    // constructRankLex + ONE placement of {keys..., cols...} (placeMany): the
+    // sorted keys in their order, then the sorted columns.  Eager (no graph
+    // cache: the record sort's eager and captured times are equal, §4f).
+    std::vector<Ciphertext<DCRTPoly>> sortRecordsLex(const std::vector<Ciphertext<DCRTPoly>>& keys,
+                                                     const std::vector<Ciphertext<DCRTPoly>>& cols,
+                                                     const std::vector<bool>& descending, SignFunc SignFunc,
+                                                     SignConfig& Cfg, size_t maxCols) {
+        const auto in = lexColumns("lexicographic record sort", keys, cols, maxCols);
+        lexDepthCheck("lexicographic record sort", keys, Cfg);
+        return placeMany(constructRankLex(keys, descending, SignFunc, Cfg), in);
+    }
+    // constructRankLex + selectRanksMany of {keys..., cols...} (eager, §4g)
+    std::vector<Ciphertext<DCRTPoly>> selectRecordsLex(const std::vector<Ciphertext<DCRTPoly>>& keys,
+                                                       const std::vector<Ciphertext<DCRTPoly>>& cols,
+                                                       const std::vector<int>& targets,
+                                                       const std::vector<bool>& descending, SignFunc SignFunc,
+                                                       SignConfig& Cfg, size_t maxCols) {
+        const auto in = lexColumns("lexicographic record selection", keys, cols, maxCols);
+        return selectRanksMany(constructRankLex(keys, descending, SignFunc, Cfg), in, targets);
     }
 
     // ---- hybrid placement I (reference :815-891,

@@ -110,6 +110,12 @@ struct SorterBase {
                                             const std::vector<int>& targets) = 0;
     virtual std::vector<Ct> selectRecords(const Ct& keys, const std::vector<Ct>& cols, const std::vector<int>& targets,
                                           SignConfig& cfg, bool stable) = 0;
+    virtual Ct rankLex(const std::vector<Ct>& keys, const std::vector<bool>& desc, SignConfig& cfg) = 0;
+    virtual std::vector<Ct> sortRecordsLex(const std::vector<Ct>& keys, const std::vector<Ct>& cols,
+                                           const std::vector<bool>& desc, SignConfig& cfg) = 0;
+    virtual std::vector<Ct> selectRecordsLex(const std::vector<Ct>& keys, const std::vector<Ct>& cols,
+                                             const std::vector<int>& targets, const std::vector<bool>& desc,
+                                             SignConfig& cfg) = 0;
     virtual Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) = 0;
     virtual Ct hybrid(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk, int variant) = 0;
     virtual Ct place2N(const Ct& rank, const Ct& in) = 0;
@@ -163,6 +169,18 @@ struct Sorter : SorterBase {
     std::vector<Ct> selectRecords(const Ct& keys, const std::vector<Ct>& cols, const std::vector<int>& targets,
                                   SignConfig& cfg, bool stable) override {
         return ds.selectRecords(keys, cols, targets, SignFunc::CompositeSign, cfg, stable);
+    }
+    Ct rankLex(const std::vector<Ct>& keys, const std::vector<bool>& desc, SignConfig& cfg) override {
+        return ds.constructRankLex(keys, desc, SignFunc::CompositeSign, cfg);
+    }
+    std::vector<Ct> sortRecordsLex(const std::vector<Ct>& keys, const std::vector<Ct>& cols,
+                                   const std::vector<bool>& desc, SignConfig& cfg) override {
+        return ds.sortRecordsLex(keys, cols, desc, SignFunc::CompositeSign, cfg, SFHE_MAX_COLUMNS);
+    }
+    std::vector<Ct> selectRecordsLex(const std::vector<Ct>& keys, const std::vector<Ct>& cols,
+                                     const std::vector<int>& targets, const std::vector<bool>& desc,
+                                     SignConfig& cfg) override {
+        return ds.selectRecordsLex(keys, cols, targets, desc, SignFunc::CompositeSign, cfg, SFHE_MAX_COLUMNS);
     }
     Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) override {
         return ds.sort_hybrid1(in, SignFunc::CompositeSign, cfg, sk);
@@ -402,6 +420,14 @@ int sfhe_tie_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
     auto s = c->cc->GetOpStats();
     *fused = s.tie_fused;
     *composed = s.tie_composed;
+    return SFHE_OK;
+}
+
+int sfhe_lex_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
+    REQUIRE(c && fused && composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *fused = s.lex_fused;
+    *composed = s.lex_composed;
     return SFHE_OK;
 }
 
@@ -768,6 +794,83 @@ int sfhe_sorter_select_records(sfhe_sorter* s, const sfhe_ct* keys, const sfhe_c
         *keys_out = wrap(got[0]);
         for (size_t i = 0; i < ncols; ++i) outs[i] = wrap(got[i + 1]);
     });
+}
+
+// the key columns and their direction flags of a lexicographic call
+static int lexKeys(const sfhe_ct* const* keys, size_t nkeys, const int* descending, size_t ncols,
+                   std::vector<Ct>* out, std::vector<bool>* desc) {
+    REQUIRE(nkeys >= 1 && nkeys <= SFHE_LEX_KEYS, "key count out of range (1 .. SFHE_LEX_KEYS)");
+    REQUIRE(nkeys + ncols <= 1 + SFHE_MAX_COLUMNS,
+            "too many columns (keys and payload columns together: at most 1 + SFHE_MAX_COLUMNS)");
+    for (size_t i = 0; i < nkeys; ++i) {
+        REQUIRE(keys[i], "null key column");
+        out->push_back(keys[i]->ct);
+        desc->push_back(descending && descending[i] != 0);
+    }
+    return SFHE_OK;
+}
+
+int sfhe_lex_sort_depth(uint32_t N, int n, int dg, int df, uint32_t nkeys, uint32_t* mult_depth) {
+    REQUIRE(mult_depth, "null argument");
+    REQUIRE(validN(N), "N must be a power of two in [4, 1024]");
+    REQUIRE(nkeys >= 1 && nkeys <= SFHE_LEX_KEYS, "key count out of range (1 .. SFHE_LEX_KEYS)");
+    return guard([&] { *mult_depth = (uint32_t)sfhe::lexSortDepth((int)N, CompositeSignConfig(n, dg, df), (int)nkeys); });
+}
+
+int sfhe_sorter_rank_lex(sfhe_sorter* s, const sfhe_ct* const* keys, size_t nkeys, const int* descending, int n,
+                         int dg, int df, sfhe_ct** out) {
+    REQUIRE(s && keys && out, "null argument");
+    std::vector<Ct> k;
+    std::vector<bool> d;
+    if (int rc = lexKeys(keys, nkeys, descending, 0, &k, &d)) return rc;
+    return guard([&] {
+        auto cfg = cfgOf(n, dg, df);
+        *out = wrap(s->impl->rankLex(k, d, cfg));
+    });
+}
+
+int sfhe_sorter_sort_records_lex(sfhe_sorter* s, sfhe_ct* const* keys, size_t nkeys, const int* descending,
+                                 sfhe_ct* const* cols, size_t ncols, int n, int dg, int df, sfhe_ct** keys_out,
+                                 sfhe_ct** outs) {
+    REQUIRE(s && keys && keys_out && (ncols == 0 || (cols && outs)), "null argument");
+    for (size_t i = 0; i < ncols; ++i) REQUIRE(cols[i], "null column");
+    std::vector<Ct> k;
+    std::vector<bool> d;
+    if (int rc = lexKeys(keys, nkeys, descending, ncols, &k, &d)) return rc;
+    return guard([&] {
+        Quiet q(s->ctx->quiet);
+        auto cfg = cfgOf(n, dg, df);
+        std::vector<Ct> in;
+        for (size_t i = 0; i < ncols; ++i) in.push_back(cols[i]->ct);
+        auto sorted = s->impl->sortRecordsLex(k, in, d, cfg);
+        for (size_t i = 0; i < nkeys; ++i) keys_out[i] = wrap(sorted[i]);
+        for (size_t i = 0; i < ncols; ++i) outs[i] = wrap(sorted[nkeys + i]);
+    });
+}
+
+int sfhe_sorter_select_records_lex(sfhe_sorter* s, const sfhe_ct* const* keys, size_t nkeys, const int* descending,
+                                   const sfhe_ct* const* cols, size_t ncols, const uint32_t* targets, size_t count,
+                                   int n, int dg, int df, sfhe_ct** keys_out, sfhe_ct** outs) {
+    REQUIRE(s && keys && targets && keys_out && (ncols == 0 || (cols && outs)), "null argument");
+    for (size_t i = 0; i < ncols; ++i) REQUIRE(cols[i], "null column");
+    std::vector<Ct> k;
+    std::vector<bool> d;
+    if (int rc = lexKeys(keys, nkeys, descending, ncols, &k, &d)) return rc;
+    std::vector<int> t;
+    if (int rc = selectTargets(s, targets, count, s->impl->size(), &t)) return rc;
+    return guard([&] {
+        auto cfg = cfgOf(n, dg, df);
+        std::vector<Ct> in;
+        for (size_t i = 0; i < ncols; ++i) in.push_back(cols[i]->ct);
+        auto got = s->impl->selectRecordsLex(k, in, t, d, cfg);
+        for (size_t i = 0; i < nkeys; ++i) keys_out[i] = wrap(got[i]);
+        for (size_t i = 0; i < ncols; ++i) outs[i] = wrap(got[nkeys + i]);
+    });
+}
+
+int sfhe_eval_lex_step(sfhe_ctx* c, const sfhe_ct* v, const sfhe_ct* q, const sfhe_ct* u, sfhe_ct** out) {
+    REQUIRE(c && v && q && u && out, "null argument");
+    return guard([&] { *out = wrap(c->cc->EvalLexStep(v->ct, q->ct, u->ct)); });
 }
 
 int sfhe_sorter_sort_hybrid1(sfhe_sorter* s, sfhe_ct* in, int n, int dg, int df, sfhe_ct** out) {

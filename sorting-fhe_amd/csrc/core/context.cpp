@@ -3239,6 +3239,76 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalTieTerm(const Ciphertext<D
     return SfheInternal::traced(this, SfheInternal::rescale(this, r->c0, r->c1, level + 1, slots), "EvalTieTerm");
 }
 
+// One tensor at u's level over the three operands: (kr - q) u carries
+// Delta_q Delta_u, and v, lifted by the integer lr = round(Delta_q Delta_u /
+// Delta_v) (exact up to a relative 2^-41 of its value, as lazyAdd's lift),
+// the same scale.  One relinearisation, one rescale; the result's scale
+// field is Delta_q Delta_u / q_dropped.
+Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalLexStep(const Ciphertext<DCRTPoly>& v,
+                                                             const Ciphertext<DCRTPoly>& q,
+                                                             const Ciphertext<DCRTPoly>& u) {
+    OpLock g(st.get());
+    SfheInternal::deps(st.get(), {&v, &q, &u});
+    SfheContextState* s = st.get();
+    if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalLexStep");
+    const uint32_t level = u->level, ell = s->ellOf(level);
+    if (v->level > level || q->level > level)
+        SFHE_THROW("EvalLexStep: v and q must have at least u's limbs (levels " + std::to_string(v->level) + ", " +
+                   std::to_string(q->level) + " against u's " + std::to_string(level) + ")");
+    if (ell < 2) SFHE_THROW("no levels left (the lexicographic step consumes one level)");
+    const uint32_t slots = std::max(std::max(v->slots, q->slots), u->slots);
+    // v's and q's rows over u's limbs: a prefix of their own, gathered where
+    // theirs are dealt over the ranks and u's level is replicated
+    std::vector<DeviceBufferPtr> keep;
+    auto rowsOf = [&](const Ciphertext<DCRTPoly>& x, const uint64_t*& x0, const uint64_t*& x1) {
+        x0 = x->c0;
+        x1 = x->c1;
+        if (s->shardAt(s->ellOf(x->level)) && !s->shardAt(ell)) {
+            keep.push_back(SfheInternal::gatherRows(s, x->c0, x->c1, ell));
+            x0 = keep.back()->ptr;
+            x1 = x0 + (size_t)ell * s->n;
+        }
+    };
+    const uint64_t *v0, *v1, *q0, *q1;
+    rowsOf(v, v0, v1);
+    rowsOf(q, q0, q1);
+    const auto kr = SfheInternal::constResidues(s, q->scale, ell);
+    const auto lr = SfheInternal::constResidues(s, q->scale * u->scale / v->scale, ell);
+    const size_t pw = s->polyWords(level);
+    const sfp_limbs m = s->qmap(ell);
+    auto t = s->alloc(3 * pw);
+    uint64_t* d0 = t->ptr;
+    uint64_t* d1 = d0 + pw;
+    uint64_t* d2 = d1 + pw;
+    const char* knob = std::getenv("SFHE_LEX_FUSED");  // (read per call: tests switch it)
+    const bool fused = sfp_lex_tensor && !(knob && *knob == '0') && !s->shardAt(ell) &&
+                       sfp_lex_tensor(s->dev, d0, d1, d2, v0, v1, q0, q1, u->c0, u->c1, kr.data(), lr.data(), m) == 0;
+    if (fused) {
+        s->stats.lex_fused++;
+    } else {  // the same integers from the generic prims: a = kr - q, the tensor of a and u, then + lr v
+        auto a = s->alloc(4 * pw);
+        uint64_t* a0 = a->ptr;
+        uint64_t* a1 = a0 + pw;
+        uint64_t* l0 = a1 + pw;
+        uint64_t* l1 = l0 + pw;
+        sfp_neg(s->dev, a0, q0, m);
+        sfp_neg(s->dev, a1, q1, m);
+        sfp_add_const(s->dev, a0, a0, kr.data(), m);
+        sfp_tensor(s->dev, d0, d1, d2, a0, a1, u->c0, u->c1, m);
+        sfp_mul_const(s->dev, l0, v0, lr.data(), m);
+        sfp_mul_const(s->dev, l1, v1, lr.data(), m);
+        sfp_add(s->dev, d0, d0, l0, m);
+        sfp_add(s->dev, d1, d1, l1, m);
+        s->stats.lex_composed++;
+    }
+    s->stats.constmult++;
+    s->stats.tensor++;
+    s->countBytes(9.0 * ell * s->n * 8);  // six rows read, three written per limb (the fused form; modelled)
+    auto r = SfheInternal::relinRescale(this, d0, d1, d2, level, slots);
+    r->scale = q->scale * u->scale / (double)s->primes[ell - 1];
+    return SfheInternal::traced(this, r, "EvalLexStep");
+}
+
 std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultMany(
     const std::vector<Ciphertext<DCRTPoly>>& a0, const std::vector<Ciphertext<DCRTPoly>>& b0) {
     OpLock g(st.get());

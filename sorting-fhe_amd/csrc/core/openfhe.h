@@ -392,6 +392,23 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     // sfp_mul, sfp_add_const and sfp_tensor compose the same integers.
     // OpStats tie_fused / tie_composed count the calls of each kind.
     Ciphertext<DCRTPoly> EvalTieTerm(const Ciphertext<DCRTPoly>& s, const Plaintext& W, double k);
+    // Engine extension (the lexicographic rank's Horner step):
+    // v + (1 - q) (.) u, relinearised, one level below u, from a single
+    // relinearisation and a single rescale.  q and v may have more limbs than
+    // u (a numerically lower level) and are read over u's limbs.  q keeps its
+    // own scale Delta_q: the constant 1 enters as the residues of Delta_q and v
+    // is lifted by the integer round(Delta_q Delta_u / Delta_v), so the three
+    // summands of the tensor carry one scale and their sum is exact.  The
+    // result's scale field holds Delta_q Delta_u / q_dropped (the level's
+    // nominal scale up to the drift between two levels' scales, ~1e-7
+    // relative); the next step, level adjustments and decryption read that
+    // field.  The tensor is one launch where the backend has prims.h
+    // sfp_lex_tensor; elsewhere (the C oracle, SFHE_LEX_FUSED=0 -- read per
+    // call --, a level whose rows are dealt over ranks, or the prim declining)
+    // the generic prims compose the same integers.  OpStats lex_fused /
+    // lex_composed count the calls of each kind.
+    Ciphertext<DCRTPoly> EvalLexStep(const Ciphertext<DCRTPoly>& v, const Ciphertext<DCRTPoly>& q,
+                                     const Ciphertext<DCRTPoly>& u);
     // Engine extension: EvalMult(a_i, b_i) for independent pairs, each formed
     // canonically (rescaled: the values a lazy product takes when its
     // consumer needs the canonical form); pairs at one level run as batched
@@ -715,6 +732,7 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         // multi-column selections: columns served; EvalRotateFoldMany's launches of
         // sfp_ks_inner_aut_sum_cols / columns it passed to EvalRotateFold
         uint64_t select_columns = 0, fold_cols_fused = 0, fold_cols_composed = 0;
+        uint64_t lex_fused = 0, lex_composed = 0;  // EvalLexStep tensors in one launch / composed of generic prims
     };
     OpStats GetOpStats() const;
     void ResetOpStats();
@@ -797,7 +815,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 11
+#define SFHE_FACADE_ABI_VERSION 12
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

@@ -2132,6 +2132,66 @@ __global__ __launch_bounds__(kThreads) void k_tie_tensor(u64* __restrict__ d0, u
     }
 }
 
+// The lexicographic rank's Horner step (prims.h sfp_lex_tensor): the tensor of
+// (a0, a1) = (kr - q0, -q1) with (u0, u1), plus lr (v0, v1) on d0 and d1, a
+// formed in registers -- six rows read and three written per limb.  a0 and a1
+// are the canonical residues sfp_neg / sfp_add_const would have stored; each
+// output is ONE reduction of the exact sum of its products, which is the
+// canonical residue the composed form reaches through its reduced
+// intermediates (sfp_tensor, sfp_mul_const, sfp_add), so the two agree residue
+// for residue.  d1 sums three products of canonical residues of primes below
+// 2^60: less than 3 * 2^120 < 2^122, inside the 128-bit accumulator.
+static_assert(2 * sizeof(ConstArgs) + 9 * sizeof(void*) + sizeof(sfp_limbs) + 8 <= 4096,
+              "k_lex_tensor's argument block exceeds the 4 KB kernel-argument limit");
+__global__ __launch_bounds__(kThreads) void k_lex_tensor(u64* __restrict__ d0, u64* __restrict__ d1,
+                                                         u64* __restrict__ d2, const u64* __restrict__ v0,
+                                                         const u64* __restrict__ v1, const u64* __restrict__ q0,
+                                                         const u64* __restrict__ q1, const u64* __restrict__ u0,
+                                                         const u64* __restrict__ u1, const ConstArgs kr,
+                                                         const ConstArgs lr, sfp_limbs m,
+                                                         const sf_barrett* __restrict__ bar, uint32_t logn) {
+    // two coefficients per thread (16-byte loads and stores)
+    const size_t pairs = ((size_t)m.count << logn) >> 1;
+    for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < pairs;
+         i += (size_t)gridDim.x * kThreads) {
+        const uint32_t limb = (uint32_t)((2 * i) >> logn);
+        const sf_barrett B = loadBar(bar, primeOf(m, limb));
+        const u64 q = B.q, kk = kr.k[limb], ll = lr.k[limb];
+        const ulonglong2 x0 = reinterpret_cast<const ulonglong2*>(v0)[i];
+        const ulonglong2 x1 = reinterpret_cast<const ulonglong2*>(v1)[i];
+        const ulonglong2 e0 = reinterpret_cast<const ulonglong2*>(q0)[i];
+        const ulonglong2 e1 = reinterpret_cast<const ulonglong2*>(q1)[i];
+        const ulonglong2 y0 = reinterpret_cast<const ulonglong2*>(u0)[i];
+        const ulonglong2 y1 = reinterpret_cast<const ulonglong2*>(u1)[i];
+        ulonglong2 a0, a1;
+        a0.x = sf_add(sf_neg(e0.x, q), kk, q);
+        a0.y = sf_add(sf_neg(e0.y, q), kk, q);
+        a1.x = sf_neg(e1.x, q);
+        a1.y = sf_neg(e1.y, q);
+        Acc s{0, 0}, t{0, 0}, w{0, 0}, z{0, 0};
+        macc(s, ll, x0.x);  // d0: two products, < 2^121
+        macc(s, a0.x, y0.x);
+        macc(t, ll, x0.y);
+        macc(t, a0.y, y0.y);
+        macc(w, ll, x1.x);  // d1: three products, < 3 * 2^120
+        macc(w, a0.x, y1.x);
+        macc(w, a1.x, y0.x);
+        macc(z, ll, x1.y);
+        macc(z, a0.y, y1.y);
+        macc(z, a1.y, y0.y);
+        ulonglong2 r0, r1, r2;
+        r0.x = sf_reduce128_acc(s.lo, s.hi, &B);
+        r0.y = sf_reduce128_acc(t.lo, t.hi, &B);
+        r1.x = sf_reduce128_acc(w.lo, w.hi, &B);
+        r1.y = sf_reduce128_acc(z.lo, z.hi, &B);
+        r2.x = bmul(a1.x, y1.x, B);
+        r2.y = bmul(a1.y, y1.y, B);
+        reinterpret_cast<ulonglong2*>(d0)[i] = r0;
+        reinterpret_cast<ulonglong2*>(d1)[i] = r1;
+        reinterpret_cast<ulonglong2*>(d2)[i] = r2;
+    }
+}
+
 struct PtrList {
     const u64* p[SFP_MAX_WSUM];
 };
@@ -5667,6 +5727,35 @@ int sfp_tie_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const u
     const size_t total = (size_t)m.count * d->n;
     SFP_GO(k_tie_tensor, dim3(ewGrid(total / 2)), dim3(kThreads), d0, d1, d2, s0, s1, w, ka, m, d->bar, d->logn);
     checkLaunch(d, "tie_tensor");
+    return 0;
+}
+
+int sfp_lex_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const uint64_t* v0, const uint64_t* v1,
+                   const uint64_t* q0, const uint64_t* q1, const uint64_t* u0, const uint64_t* u1, const uint64_t* kr,
+                   const uint64_t* lr, sfp_limbs m) {
+    // both constant arrays ride in the kernel's argument block (no upload, no
+    // ring slot: capturable, any lane); 16-byte accesses need aligned rows
+    if (!m.count || m.count > SFP_MAX_LIMBS || d->n < 2) return -1;
+    uint64_t* const outs[3] = {d0, d1, d2};
+    const uint64_t* const ins[6] = {v0, v1, q0, q1, u0, u1};
+    const size_t words = (size_t)m.count * d->n;
+    const uintptr_t bytes = words * 8;
+    for (const uint64_t* o : outs) {
+        if ((uintptr_t)o & 15) return -1;
+        for (const uint64_t* in : ins)  // (the kernel's pointers are __restrict__)
+            if ((uintptr_t)o < (uintptr_t)in + bytes && (uintptr_t)in < (uintptr_t)o + bytes) return -1;
+    }
+    for (const uint64_t* in : ins)
+        if ((uintptr_t)in & 15) return -1;
+    if (!limbsOk(d, m, "lex_tensor")) return -1;
+    ConstArgs ka, la;
+    std::memcpy(ka.k, kr, m.count * 8);
+    std::memset(ka.k + m.count, 0, (SFP_MAX_LIMBS - m.count) * 8);
+    std::memcpy(la.k, lr, m.count * 8);
+    std::memset(la.k + m.count, 0, (SFP_MAX_LIMBS - m.count) * 8);
+    SFP_GO(k_lex_tensor, dim3(ewGrid(words / 2)), dim3(kThreads), d0, d1, d2, v0, v1, q0, q1, u0, u1, ka, la, m, d->bar,
+           d->logn);
+    checkLaunch(d, "lex_tensor");
     return 0;
 }
 

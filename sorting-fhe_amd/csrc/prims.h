@@ -376,6 +376,25 @@ SFP_OPTIONAL int sfp_const_terms_rescale(sfp_dev* d, const uint64_t* in, size_t 
 SFP_OPTIONAL int sfp_tie_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const uint64_t* s0,
                                 const uint64_t* s1, const uint64_t* w, const uint64_t* k, sfp_limbs m);
 
+// ---- optional: the lexicographic rank's Horner step (sort by several keys) -------
+// With (a0, a1) = (kr - q0, -q1) -- q, v and u ciphertexts, kr[limb] and
+// lr[limb] host residues, all m.count rows in the evaluation domain -- the
+// tensor of a and u plus lr v in ONE launch:
+//   d0 = lr v0 + a0 u0,  d1 = lr v1 + a0 u1 + a1 u0,  d2 = a1 u1
+// i.e. lr v + (kr - q) (.) u before its relinearisation.  a is never stored.
+// The canonical residues of sfp_neg (q0, q1), sfp_add_const (+ kr),
+// sfp_tensor(a, u), sfp_mul_const (lr v0, lr v1) and two sfp_add: eight
+// launches.  Each output is one reduction of the exact sum of its products
+// (d1: three products of residues below 2^60, under 3 * 2^120).  kr and lr
+// travel in the kernel's arguments: no upload and no host synchronisation, so
+// the prim may be captured and issued on any lane.  Weak like the prims above:
+// where its address is null (the C oracle), or it returns -1 with nothing
+// written (more than SFP_MAX_LIMBS rows, a row not 16-byte aligned, an output
+// overlapping an input), the host layer runs the generic prims.
+SFP_OPTIONAL int sfp_lex_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const uint64_t* v0,
+                                const uint64_t* v1, const uint64_t* q0, const uint64_t* q1, const uint64_t* u0,
+                                const uint64_t* u1, const uint64_t* kr, const uint64_t* lr, sfp_limbs m);
+
 // ---- optional: the giant-step sums of several columns under one plaintext set ----
 // nc columns (records' payloads placed by one rank) share the ng x nin
 // plaintexts b[g * nin + j] of sfp_mac_plain2_multi; column c has its own

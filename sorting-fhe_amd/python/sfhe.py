@@ -54,9 +54,12 @@ ABI_SYMBOLS = [
     "sfhe_select_params", "sfhe_sorter_select_ranked", "sfhe_sorter_select", "sfhe_eval_rotate_fold",
     "sfhe_select_counts",
     "sfhe_sorter_select_many", "sfhe_sorter_select_records", "sfhe_eval_rotate_fold_many", "sfhe_select_cols_counts",
+    "sfhe_lex_sort_depth", "sfhe_sorter_rank_lex", "sfhe_sorter_sort_records_lex", "sfhe_sorter_select_records_lex",
+    "sfhe_eval_lex_step", "sfhe_lex_counts",
 ]
 
 MAX_COLUMNS = 8  # SFHE_MAX_COLUMNS
+LEX_KEYS = 4  # SFHE_LEX_KEYS
 
 
 class SfheError(RuntimeError):
@@ -198,6 +201,14 @@ _SIGS = {
                                              _PVP, _PVP]),
     "sfhe_eval_rotate_fold_many": (C.c_int, [_VP, _PVP, _SZ, C.c_int32, _U32, _PVP]),
     "sfhe_select_cols_counts": (C.c_int, [_VP, _PU64, _PU64, _PU64]),
+    "sfhe_lex_sort_depth": (C.c_int, [_U32, C.c_int, C.c_int, C.c_int, _U32, _PU32]),
+    "sfhe_sorter_rank_lex": (C.c_int, [_VP, _PVP, _SZ, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, _PVP]),
+    "sfhe_sorter_sort_records_lex": (C.c_int, [_VP, _PVP, _SZ, C.POINTER(C.c_int), _PVP, _SZ, C.c_int, C.c_int,
+                                               C.c_int, _PVP, _PVP]),
+    "sfhe_sorter_select_records_lex": (C.c_int, [_VP, _PVP, _SZ, C.POINTER(C.c_int), _PVP, _SZ, _PU32, _SZ, C.c_int,
+                                                 C.c_int, C.c_int, _PVP, _PVP]),
+    "sfhe_eval_lex_step": (C.c_int, [_VP, _VP, _VP, _VP, _PVP]),
+    "sfhe_lex_counts": (C.c_int, [_VP, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -512,6 +523,17 @@ class Engine:
         self._chk(self.lib.sfhe_tie_counts(self.ctx, C.byref(f), C.byref(c)))
         return f.value, c.value
 
+    def lex_step(self, v, q, u):
+        """v + (1 - q) * u, one level below u (one relinearisation, one rescale): the
+        lexicographic rank's Horner step.  v and q may sit at a numerically lower level than u."""
+        return self._new(self.lib.sfhe_eval_lex_step, self.ctx, v.h, q.h, u.h)
+
+    def lex_counts(self):
+        """(fused, composed) lex_step tensors (rank_lex's included) since the last op_stats reset."""
+        f, c = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_lex_counts(self.ctx, C.byref(f), C.byref(c)))
+        return f.value, c.value
+
     def place_counts(self):
         """(hits, columns, fused, composed) of multi-column placements since the last op_stats
         reset: indicators evaluated, columns they served, giant-step sums formed by
@@ -776,6 +798,55 @@ class Sorter:
         return self.select_records(keys, cts, [self.N - 1 - i for i in range(k)] if largest else list(range(k)),
                                    **kw)
 
+    # -- ORDER BY several keys --
+    @staticmethod
+    def _lex(keys, descending):
+        keys = list(keys)
+        desc = [False] * len(keys) if descending is None else [bool(d) for d in descending]
+        if len(desc) != len(keys):
+            raise SfheError("sfhe error -1: one descending flag per key is needed")
+        hs = (_VP * max(len(keys), 1))(*[k.h if k is not None else None for k in keys])
+        return keys, hs, (C.c_int * max(len(keys), 1))(*[int(d) for d in desc])
+
+    def rank_lex(self, keys, descending=None, n: int = 3, dg: int = 2, df: int = 2) -> Ct:
+        """The rank of every row in (keys[0], keys[1], ..., input index) order, key i descending
+        where descending[i]; 1 .. LEX_KEYS keys at one level.  len(keys) - 1 levels below
+        rank_stable; with one ascending key exactly its residues."""
+        keys, hs, ds = self._lex(keys, descending)
+        return self.eng._new(self.eng.lib.sfhe_sorter_rank_lex, self.h, hs, len(keys), ds, n, dg, df)
+
+    def sort_records_lex(self, keys, cts=(), descending=None, n: int = 3, dg: int = 2, df: int = 2):
+        """ORDER BY keys[0], keys[1], ... over rows: ([sorted key columns], [payload columns in
+        that order]); rows equal on every key keep their input order.  The context needs
+        lex_sort_depth(N, (n, dg, df), len(keys)) levels (SfheError otherwise)."""
+        keys, hs, ds = self._lex(keys, descending)
+        cts = list(cts)
+        cs = (_VP * max(len(cts), 1))(*[c.h if c is not None else None for c in cts])
+        kouts = (_VP * max(len(keys), 1))()
+        outs = (_VP * max(len(cts), 1))()
+        self.eng._chk(self.eng.lib.sfhe_sorter_sort_records_lex(self.h, hs, len(keys), ds, cs, len(cts), n, dg, df,
+                                                                kouts, outs))
+        return ([Ct(self.eng, C.c_void_p(kouts[i])) for i in range(len(keys))],
+                [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cts))])
+
+    def select_records_lex(self, keys, cts=(), targets=(0,), descending=None, n: int = 3, dg: int = 2, df: int = 2):
+        """ORDER BY keys ... LIMIT: the rows whose lexicographic ranks are `targets`, as
+        ([key columns' rows], [payload columns' rows]).  Needs the rotations of select_params."""
+        keys, hs, ds = self._lex(keys, descending)
+        cts = list(cts)
+        buf, k = self._targets(targets)
+        cs = (_VP * max(len(cts), 1))(*[c.h if c is not None else None for c in cts])
+        kouts = (_VP * max(len(keys), 1))()
+        outs = (_VP * max(len(cts), 1))()
+        self.eng._chk(self.eng.lib.sfhe_sorter_select_records_lex(self.h, hs, len(keys), ds, cs, len(cts), buf, k,
+                                                                  n, dg, df, kouts, outs))
+        return ([Ct(self.eng, C.c_void_p(kouts[i])) for i in range(len(keys))],
+                [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cts))])
+
+    def top_k_records_lex(self, keys, cts, k: int, descending=None, **kw):
+        """The first k rows in (keys, input index) order."""
+        return self.select_records_lex(keys, cts, list(range(k)), descending, **kw)
+
     def top_k(self, ct: Ct, k: int, largest: bool = False, **kw) -> Ct:
         """The k smallest values in ascending order (largest: the k largest, descending)."""
         return self.select(ct, [self.N - 1 - i for i in range(k)] if largest else list(range(k)), **kw)
@@ -853,6 +924,17 @@ def select_params(N: int, backend: str = "hip"):
     buf = (C.c_int32 * cnt.value)()
     lib.sfhe_select_params(N, None, buf, cnt.value, None)
     return depth.value, list(buf)
+
+
+def lex_sort_depth(N: int, cfg=None, m: int = 2, backend: str = "hip") -> int:
+    """mult_depth of Sorter.sort_records_lex by m keys with sign configuration cfg = (n, dg, df)
+    (None: (3, 2, 2), the methods' default): the stable sort's depth + m - 1."""
+    lib = load(backend)
+    n, dg, df = (3, 2, 2) if cfg is None else cfg
+    depth = C.c_uint32()
+    if lib.sfhe_lex_sort_depth(N, int(n), int(dg), int(df), int(m), C.byref(depth)) != SFHE_OK:
+        raise SfheError(lib.sfhe_last_error().decode())
+    return depth.value
 
 
 class KWay:
