@@ -38,7 +38,8 @@ extern "C" {
  * sfhe_eval_rotate_fold_many, sfhe_select_cols_counts, and the ordering by
  * several keys: SFHE_LEX_KEYS, sfhe_lex_sort_depth, sfhe_sorter_rank_lex,
  * sfhe_sorter_sort_records_lex, sfhe_sorter_select_records_lex,
- * sfhe_eval_lex_step, sfhe_lex_counts) */
+ * sfhe_eval_lex_step, sfhe_lex_counts, and the sum of two products:
+ * sfhe_eval_mult_sum2, sfhe_dot_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -394,6 +395,18 @@ int sfhe_sorter_select_records_lex(sfhe_sorter* s, const sfhe_ct* const* keys, s
  * composes; the results are bit-identical). */
 int sfhe_eval_lex_step(sfhe_ctx* c, const sfhe_ct* v, const sfhe_ct* q, const sfhe_ct* u, sfhe_ct** out);
 int sfhe_lex_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
+/* Rescale(Relin(a (x) b + a2 (x) b2)) + r, one level below the operands: the
+ * sum of two products with one relinearisation, ModDown and rescale (the sign
+ * polynomials' paired products).  The four operands at one level (a product
+ * among them is settled first); r: null, or a ciphertext at the result's level.
+ * sfhe_dot_counts: such sums that ran as one fused launch chain
+ * (sfp_mult2_relin_rescale_add) and as the composed generic prims since the
+ * last sfhe_op_stats reset (SFHE_MULT_SUM2_FUSED=0, read per call, composes;
+ * the results are bit-identical).  SFHE_SIGN_DOT=0 (read per call) keeps the
+ * sign polynomials on two separate products. */
+int sfhe_eval_mult_sum2(sfhe_ctx* c, const sfhe_ct* a, const sfhe_ct* b, const sfhe_ct* a2, const sfhe_ct* b2,
+                        const sfhe_ct* r, sfhe_ct** out);
+int sfhe_dot_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
 /* nodes of the captured record sort (0 while none); sfhe_sorter_graph_nodes
  * keeps reporting the plain / stable sort's graph */
 int sfhe_sorter_records_graph_nodes(const sfhe_sorter* s, uint64_t* nodes);

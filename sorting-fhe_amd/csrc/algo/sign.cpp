@@ -30,6 +30,13 @@ Ct constTermAt(const CryptoContext<DCRTPoly>& cc, const Ct& x, double c, uint32_
     return cc->LinearWSumRescale(i0, i1, w, at - 1, x->GetSlots(), &sc);
 }
 
+// SFHE_SIGN_DOT=0 (read per call): a node and its `lo` child keep their two
+// separate products (see OddPoly).
+bool signDot() {
+    const char* v = std::getenv("SFHE_SIGN_DOT");
+    return !v || *v != '0';
+}
+
 // sum_{i} c[i] x^(2i+1) for c.size() == 2^(k-1) odd coefficients, depth k:
 //   P(x) = A(x) + B(x) * x^(2^(k-1)),  A,B of half the degree.
 // pw[j] holds x^(2^(j+1)) (x^2, x^4, x^8, ...).
@@ -42,11 +49,21 @@ Ct constTermAt(const CryptoContext<DCRTPoly>& cc, const Ct& x, double c, uint32_
 // power x^(2^j) may need aligning, once per level (memo).  Degree 7: 10
 // rescales instead of 12 (4 coefficient products, 5 ciphertext products, x^2
 // aligned once); same depth and polynomial.
+//
+// Paired products: where a node's `lo` child A is itself a product node,
+//   A + B x^(2^j) = A.lo + A.hi x^(2^j') + B x^(2^j),
+// both products work at the node's level (`want` lands A there: operands at
+// Lp - 1) and are only added, so they go out as ONE sum of two products
+// (EvalMultSum2: one relinearisation, ModDown and rescale) with A.lo as its
+// addend.  Degree 7 pairs at the root ((c3 x) x^2 with B x^4, addend c1 x);
+// degree 15 at the root and at the root's `hi` child.  A.lo and B are whole
+// nodes of their own (and pair again where the rule holds).
 struct OddPoly {
     const CryptoContext<DCRTPoly>& cc;
     const Ct& x;
     const std::vector<Ct>& pw;
     std::map<std::pair<size_t, uint32_t>, Ct> aligned;
+    const bool dot = signDot();
 
     Ct constAt(double c, uint32_t at) { return constTermAt(cc, x, c, at); }
     const Ct& power(size_t j, uint32_t level) {
@@ -72,6 +89,16 @@ struct OddPoly {
         const size_t half = cnt / 2, j = powIndex(half);
         const uint32_t Lp = std::max(std::max(natural(half), pw[j]->GetLevel()) + 1, want);
         Ct hi = eval(c + half, half, Lp - 1);
+        if (dot && half > 1) {
+            const size_t half2 = half / 2, j2 = powIndex(half2);
+            if (std::max(std::max(natural(half2), pw[j2]->GetLevel()) + 1, Lp) == Lp) {  // (the child's level)
+                Ct hi2 = eval(c + half2, half2, Lp - 1);
+                Ct lolo = eval(c, half2, Lp);
+                const Ct p1 = power(j, Lp - 1), p2 = power(j2, Lp - 1);
+                for (const Ct& o : {hi, p1, hi2, p2, lolo}) cc->Settle(o);
+                return cc->EvalMultSum2(hi, p1, hi2, p2, lolo);
+            }
+        }
         Ct prod = cc->EvalMult(hi, power(j, Lp - 1));
         Ct lo = eval(c, half, Lp);
         return cc->EvalAdd(lo, prod);
@@ -102,6 +129,9 @@ bool signBatch() {
 // the operands it saw in OddPoly::eval, in the same form: a product's sum
 // partner `lo` is canonical at the product's own level (`want` lands it
 // there), so the sum takes the product's canonical form there as well.
+// A paired node (OddPoly: its `lo` child is a product node) issues its own and
+// the child's product as one EvalMultSum2 once the operands of both and the
+// child's `lo` exist; the child forms no product or sum of its own.
 struct OddPolyWaves {
     const CryptoContext<DCRTPoly>& cc;
     const Ct& x;
@@ -112,10 +142,13 @@ struct OddPolyWaves {
         uint32_t Lp;  // a leaf's level / the level of the node's product and sum
         int hi, lo;
         Ct prod, out;
+        int pair = -1;          // the `lo` child whose product rides in this node's EvalMultSum2
+        bool absorbed = false;  // such a child
     };
     std::vector<Node> nodes;
     std::vector<Ct> pw;
     std::map<std::pair<size_t, uint32_t>, Ct> aligned;
+    const bool dot = signDot();
 
     uint32_t pwLevel(size_t j) const { return L + 1 + (uint32_t)j; }
     uint32_t natural(size_t cnt) const {
@@ -134,6 +167,15 @@ struct OddPolyWaves {
             nd.Lp = std::max(std::max(natural(half), pwLevel(nd.j)) + 1, want);
             nd.hi = build(c + half, half, nd.Lp - 1);
             nd.lo = build(c, half, nd.Lp);
+            if (dot && nodes[nd.lo].cnt > 1 && nodes[nd.lo].Lp == nd.Lp) {
+                nd.pair = nd.lo;
+                Node& ch = nodes[nd.lo];
+                ch.absorbed = true;
+                if (ch.pair >= 0) {  // (its own `lo` is this node's addend: a whole node again)
+                    nodes[ch.pair].absorbed = false;
+                    ch.pair = -1;
+                }
+            }
         }
         nodes.push_back(nd);
         return (int)nodes.size() - 1;
@@ -154,24 +196,34 @@ struct OddPolyWaves {
             // earlier wave that a node wants at a higher level is aligned after
             // this wave's products (once per level), for the next wave
             std::vector<std::pair<size_t, uint32_t>> align;
+            // a node's power at its operand level; null, with the alignment asked for, while it is not there
+            auto powerOf = [&](const Node& nd) -> const Ct* {
+                if (nd.j >= ready) return nullptr;
+                if (pwLevel(nd.j) >= nd.Lp - 1) return &pw[nd.j];
+                const auto key = std::make_pair(nd.j, nd.Lp - 1);
+                auto it = aligned.find(key);
+                if (it != aligned.end()) return &it->second;
+                if (std::find(align.begin(), align.end(), key) == align.end()) align.push_back(key);
+                return nullptr;
+            };
+            size_t dots = 0;
             for (Node& nd : nodes) {
-                if (nd.cnt == 1 || nd.prod || nd.j >= ready) continue;
-                const Ct* power = &pw[nd.j];
-                if (pwLevel(nd.j) < nd.Lp - 1) {
-                    const auto key = std::make_pair(nd.j, nd.Lp - 1);
-                    auto it = aligned.find(key);
-                    if (it == aligned.end()) {
-                        if (std::find(align.begin(), align.end(), key) == align.end()) align.push_back(key);
-                        continue;
-                    }
-                    power = &it->second;
+                if (nd.cnt == 1 || nd.prod || nd.out || nd.absorbed) continue;
+                const Ct* power = powerOf(nd);
+                if (nd.pair >= 0) {  // both products and the child's `lo` in one op
+                    const Node& ch = nodes[nd.pair];
+                    const Ct* power2 = powerOf(ch);
+                    if (!power || !power2 || !nodes[nd.hi].out || !nodes[ch.hi].out || !nodes[ch.lo].out) continue;
+                    nd.out = cc->EvalMultSum2(nodes[nd.hi].out, *power, nodes[ch.hi].out, *power2, nodes[ch.lo].out);
+                    ++dots;
+                    continue;
                 }
-                if (!nodes[nd.hi].out) continue;
+                if (!power || !nodes[nd.hi].out) continue;
                 nd.prod = cc->EvalMult(nodes[nd.hi].out, *power);
                 prods.push_back(nd.prod);
             }
             const bool first = ready == 0;
-            if (prods.empty() && align.empty() && !first)
+            if (prods.empty() && align.empty() && !first && !dots)
                 throw OpenFHEException("internal: odd-polynomial wave evaluation stalled");
             cc->MaterializeMany(prods, std::vector<char>(prods.size(), 0));
             if (first) {

@@ -431,6 +431,14 @@ int sfhe_lex_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
     return SFHE_OK;
 }
 
+int sfhe_dot_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
+    REQUIRE(c && fused && composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *fused = s.dot_fused;
+    *composed = s.dot_composed;
+    return SFHE_OK;
+}
+
 int sfhe_place_counts(sfhe_ctx* c, uint64_t* hits, uint64_t* columns, uint64_t* fused, uint64_t* composed) {
     REQUIRE(c && hits && columns && fused && composed, "null argument");
     auto s = c->cc->GetOpStats();
@@ -871,6 +879,16 @@ int sfhe_sorter_select_records_lex(sfhe_sorter* s, const sfhe_ct* const* keys, s
 int sfhe_eval_lex_step(sfhe_ctx* c, const sfhe_ct* v, const sfhe_ct* q, const sfhe_ct* u, sfhe_ct** out) {
     REQUIRE(c && v && q && u && out, "null argument");
     return guard([&] { *out = wrap(c->cc->EvalLexStep(v->ct, q->ct, u->ct)); });
+}
+
+int sfhe_eval_mult_sum2(sfhe_ctx* c, const sfhe_ct* a, const sfhe_ct* b, const sfhe_ct* a2, const sfhe_ct* b2,
+                        const sfhe_ct* r, sfhe_ct** out) {
+    REQUIRE(c && a && b && a2 && b2 && out, "null argument");
+    return guard([&] {
+        for (const sfhe_ct* x : {a, b, a2, b2, r})
+            if (x) c->cc->Settle(x->ct);
+        *out = wrap(c->cc->EvalMultSum2(a->ct, b->ct, a2->ct, b2->ct, r ? r->ct : nullptr));
+    });
 }
 
 int sfhe_sorter_sort_hybrid1(sfhe_sorter* s, sfhe_ct* in, int n, int dg, int df, sfhe_ct** out) {

@@ -3479,6 +3479,77 @@ std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultManyAdd(
     return out;
 }
 
+// The sum of two products at one level, relinearised and rescaled once.
+Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMultSum2(const Ciphertext<DCRTPoly>& a,
+                                                              const Ciphertext<DCRTPoly>& b,
+                                                              const Ciphertext<DCRTPoly>& a2,
+                                                              const Ciphertext<DCRTPoly>& b2,
+                                                              const Ciphertext<DCRTPoly>& r) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    if (!a || !b || !a2 || !b2) SFHE_THROW("EvalMultSum2: null operand");
+    if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalMultSum2");
+    for (const Ciphertext<DCRTPoly>* c : {&a, &b, &a2, &b2, &r})
+        if (*c && SfheInternal::isLazy(*c))
+            SFHE_THROW("EvalMultSum2: an operand is a deferred or pending product (Settle it first)");
+    const uint32_t level = a->level, ell = s->ellOf(level);
+    if (b->level != level || a2->level != level || b2->level != level)
+        SFHE_THROW("EvalMultSum2: the operands are at levels " + std::to_string(a->level) + ", " +
+                   std::to_string(b->level) + ", " + std::to_string(a2->level) + ", " + std::to_string(b2->level) +
+                   " (one level is required)");
+    if (a->scale * b->scale != a2->scale * b2->scale)
+        SFHE_THROW("EvalMultSum2: the two products carry different scales");
+    if (ell < 2 || level + 1 > s->L) SFHE_THROW("no levels left (multiplicative depth exhausted)");
+    if (r && (r->level != level + 1 || r->scale != s->scale[level + 1]))
+        SFHE_THROW("EvalMultSum2: the addend is not canonical at the result's level " + std::to_string(level + 1));
+    SfheInternal::deps(s, {&a, &b, &a2, &b2, &r});
+    const uint32_t n = s->n;
+    uint32_t slots = std::max(std::max(a->slots, b->slots), std::max(a2->slots, b2->slots));
+    if (r) slots = std::max(slots, r->slots);
+    const size_t pw = s->polyWords(level);
+    s->stats.tensor += 2;
+    s->countBytes(2 * 7.0 * ell * n * 8);
+    const char* knob = std::getenv("SFHE_MULT_SUM2_FUSED");  // (read per call: tests switch it)
+    if (sfp_mult2_relin_rescale_add && !(knob && *knob == '0') && SfheInternal::fusedRescale() && !s->shardAt(ell) &&
+        (!r || r->c1 - r->c0 == (ptrdiff_t)s->polyWords(level + 1))) {
+        const DeviceBufferPtr& key = s->relinFor(ell);
+        const int tier = key->ksTier;
+        const uint32_t K = s->Kof(tier), beta = (ell + s->alpha - 1) / s->alpha;
+        const size_t stride = (size_t)(ell + K) * n;
+        auto out = SfheInternal::newCt(this, level + 1, slots);
+        auto acc = s->alloc(2 * stride);
+        auto ext = s->alloc(stride * beta);
+        auto scratch = s->alloc((size_t)2 * ell * n);
+        auto& convs = SfheInternal::modupConv(this, ell, tier);
+        if (sfp_mult2_relin_rescale_add(s->dev, out->c0, out->c1, a->c0, a->c1, b->c0, b->c1, a2->c0, a2->c1, b2->c0,
+                                        b2->c1, ell, K, s->Lq, s->alpha, convs.data(), key->ptr,
+                                        s->moddownConvOf(tier), s->pInvModQof(tier), s->pModQof(tier),
+                                        s->qInvTable[ell].data(), acc->ptr, ext->ptr, scratch->ptr,
+                                        r ? r->c0 : nullptr, r ? r->c1 : nullptr, 1, nullptr) == 0) {
+            s->stats.dot_fused++;
+            s->stats.keyswitch++;
+            s->stats.rescale++;
+            s->stats.add += r ? 2 : 1;
+            s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
+            s->countBytes(4.0 * ell * n * 8);
+            return SfheInternal::traced(this, out, "EvalMultSum2");
+        }
+    }
+    // composed: both tensors, their components summed, one relinearisation + rescale, then the addend
+    auto t = s->alloc(6 * pw);
+    uint64_t* d = t->ptr;
+    uint64_t* e = d + 3 * pw;
+    const sfp_limbs m = s->qmap(ell);
+    sfp_tensor(s->dev, d, d + pw, d + 2 * pw, a->c0, a->c1, b->c0, b->c1, m);
+    sfp_tensor(s->dev, e, e + pw, e + 2 * pw, a2->c0, a2->c1, b2->c0, b2->c1, m);
+    for (int i = 0; i < 3; ++i) sfp_add(s->dev, d + i * pw, d + i * pw, e + i * pw, m);
+    s->stats.add++;
+    s->stats.dot_composed++;
+    auto out = SfheInternal::relinRescale(this, d, d + pw, d + 2 * pw, level, slots);
+    if (r) out = EvalAdd(out, r);  // (both canonical at one level: one sfp_add)
+    return SfheInternal::traced(this, out, "EvalMultSum2");
+}
+
 Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMultAddPlain(
     const std::vector<Ciphertext<DCRTPoly>>& a, const std::vector<Plaintext>& p) {
     OpLock g(st.get());

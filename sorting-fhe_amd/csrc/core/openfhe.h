@@ -435,6 +435,25 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     std::vector<Ciphertext<DCRTPoly>> EvalMultManyAdd(const std::vector<Ciphertext<DCRTPoly>>& a,
                                                       const std::vector<Ciphertext<DCRTPoly>>& b,
                                                       const std::vector<MultAddend>& adds);
+    // Engine extension (the sign polynomials' paired products):
+    // Rescale(Relin(a (x) b + a2 (x) b2)) + r, one level below the operands --
+    // the value of EvalAdd(EvalAdd(EvalMult(a, b), EvalMult(a2, b2)), r) with
+    // the two tensors summed before ONE relinearisation, ModDown and rescale
+    // (one key-switch rounding instead of two).  Throws unless the four
+    // operands are settled (no deferred or pending product: Settle), at one
+    // level, with a.scale * b.scale == a2.scale * b2.scale, and r (may be null)
+    // is settled at the result's level with that level's scale.  The composed
+    // form defines the integers: sfp_tensor twice, the three components summed
+    // (sfp_add), the relinearisation with its fused ModDown + rescale, the sum
+    // with r.  Where the backend has prims.h sfp_mult2_relin_rescale_add it is
+    // one product's launch chain that reads the second pair where it reads the
+    // first; elsewhere (the C oracle, SFHE_MULT_SUM2_FUSED=0 -- read per call --,
+    // SFHE_FUSED_RESCALE=0, a level whose rows are dealt over ranks, the prim
+    // declining) the composed form runs: the same residues.  OpStats dot_fused
+    // / dot_composed count the calls of each kind.
+    Ciphertext<DCRTPoly> EvalMultSum2(const Ciphertext<DCRTPoly>& a, const Ciphertext<DCRTPoly>& b,
+                                      const Ciphertext<DCRTPoly>& a2, const Ciphertext<DCRTPoly>& b2,
+                                      const Ciphertext<DCRTPoly>& r);
     // Engine extension: sum_i a_i * p_i with ONE rescale (same value and
     // level as summing the individually rescaled EvalMult(a_i, p_i)).
     Ciphertext<DCRTPoly> EvalMultAddPlain(const std::vector<Ciphertext<DCRTPoly>>& a,
@@ -733,6 +752,7 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         // sfp_ks_inner_aut_sum_cols / columns it passed to EvalRotateFold
         uint64_t select_columns = 0, fold_cols_fused = 0, fold_cols_composed = 0;
         uint64_t lex_fused = 0, lex_composed = 0;  // EvalLexStep tensors in one launch / composed of generic prims
+        uint64_t dot_fused = 0, dot_composed = 0;  // EvalMultSum2 as one fused chain / composed of generic prims
     };
     OpStats GetOpStats() const;
     void ResetOpStats();
@@ -815,7 +835,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 12
+#define SFHE_FACADE_ABI_VERSION 13
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

@@ -833,6 +833,11 @@ struct RowGroup {
     // of polynomial p, coefficient form; pre = its dropped row l (with rescale)
     const struct MdColArgs* md;
     uint32_t esumNeg;
+    // a second product summed with the first (sfp_mult2_relin_rescale_add): a
+    // device array of its four row bases (a0', a1', b0', b1'; row i at + i n).
+    // Inverse first pass with `pre`: the rows are src * pre + a1' * b1'; forward
+    // epilogue with tA0: the tensor gains the second quadruple's products.
+    const u64* const* t2;
 };
 
 // Merged launches (stacked regions, batched ops; sfp_stack_begin /
@@ -893,7 +898,11 @@ __device__ unsigned long long g_mdrsTrace[kTraceSlots][8];  // k_mdrsf (FP64 blo
 #define NTT_MARK(i)
 #endif
 
-template <bool INV, bool COL, int LE, int TILE, int NG = 1, bool CONV = false>
+// DOT: the two-product forms (RowGroup::t2) are compiled in; the launch sites
+// pick these instantiations only for a group that carries t2, so every other
+// launch runs the kernel exactly as it compiles without them (their loads
+// cost the single-product forms up to three waves per SIMD).
+template <bool INV, bool COL, int LE, int TILE, int NG = 1, bool CONV = false, bool DOT = false>
 __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, const sf_barrett* __restrict__ bar,
                                                   const u64* __restrict__ tw, const u64* __restrict__ twS,
                                                   const u64* __restrict__ ninv,
@@ -1026,6 +1035,22 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
 #pragma unroll
         for (int k = 0; k < NPAIR; ++k) mr[k] = *reinterpret_cast<const ulonglong2*>(pre + tileOff(k));
     }
+    // (the inverse ROW pass alone: a sum of two products' d2 enters through ModUp's INTT)
+    constexpr bool kPre2 = DOT && INV && !COL;
+    ulonglong2 xr2[kPre2 ? NPAIR : 1], mr2[kPre2 ? NPAIR : 1];
+    bool pre2 = false;
+    if constexpr (kPre2) {
+        if (pre && G.t2) {
+            pre2 = true;
+            const u64* in2 = G.t2[1] + ((size_t)ii << logn);
+            const u64* pm2 = G.t2[3] + ((size_t)ii << logn);
+#pragma unroll
+            for (int k = 0; k < NPAIR; ++k) {
+                xr2[k] = *reinterpret_cast<const ulonglong2*>(in2 + tileOff(k));
+                mr2[k] = *reinterpret_cast<const ulonglong2*>(pm2 + tileOff(k));
+            }
+        }
+    }
     const u64* gwI = tw + (size_t)prime * n;
     const u64* gwD = reinterpret_cast<const u64*>(twD) + (size_t)prime * n;
     const u64* gx = twS + (size_t)prime * n;
@@ -1097,6 +1122,12 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
                 const ulonglong2 m = mr[k];
                 x.x = bmul(x.x, m.x, LB);
                 x.y = bmul(x.y, m.y, LB);
+                if constexpr (kPre2) {
+                    if (pre2) {
+                        x.x = sf_add(x.x, bmul(xr2[k].x, mr2[k].x, LB), q);
+                        x.y = sf_add(x.y, bmul(xr2[k].y, mr2[k].y, LB), q);
+                    }
+                }
             }
             if (preK) {
                 x.x = sf_mul_shoup(x.x, pk, pkS, q);
@@ -1177,6 +1208,17 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
     // (forward passes only: the inverse COL pass keeps its post factors in these fields)
     const u64* esm = !INV && epi && G.esum.base ? rowAt(G.esum, pp, ii) : nullptr;
     const u64 ecs = !INV && epi && G.ecst ? G.ecst[pp * G.R + ii] : 0;
+    // (the forward ROW pass alone: the second product's rows, sfp_mult2_relin_rescale_add)
+    constexpr bool kTens2 = DOT && !INV && !COL;
+    const u64 *uA0 = nullptr, *uA1 = nullptr, *uB0 = nullptr, *uB1 = nullptr;
+    if constexpr (kTens2) {
+        if (tens && G.t2) {
+            uA0 = G.t2[0];
+            uA1 = G.t2[1];
+            uB0 = G.t2[2];
+            uB1 = G.t2[3];
+        }
+    }
 #pragma unroll
     for (int k = 0; k < NPAIR; ++k) {
         const uint32_t e = 2 * (threadIdx.x + k * NT);
@@ -1233,7 +1275,32 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
                 if (tens) {  // the tensor product's polynomial pp at (row ii, g)
                     const ulonglong2 a0 = *reinterpret_cast<const ulonglong2*>(G.tA0 + trow + g);
                     const ulonglong2 b0 = *reinterpret_cast<const ulonglong2*>(G.tB0 + trow + g);
-                    if (pp == 0) {
+                    if (kTens2 && uA0) {  // both quadruples' products, one reduction of their exact sum
+                        const ulonglong2 c0 = *reinterpret_cast<const ulonglong2*>(uA0 + trow + g);
+                        const ulonglong2 e0 = *reinterpret_cast<const ulonglong2*>(uB0 + trow + g);
+                        Acc t{0, 0}, u{0, 0};
+                        if (pp == 0) {
+                            macc(t, a0.x, b0.x);
+                            macc(t, c0.x, e0.x);
+                            macc(u, a0.y, b0.y);
+                            macc(u, c0.y, e0.y);
+                        } else {
+                            const ulonglong2 a1 = *reinterpret_cast<const ulonglong2*>(G.tA1 + trow + g);
+                            const ulonglong2 b1 = *reinterpret_cast<const ulonglong2*>(G.tB1 + trow + g);
+                            const ulonglong2 c1 = *reinterpret_cast<const ulonglong2*>(uA1 + trow + g);
+                            const ulonglong2 e1 = *reinterpret_cast<const ulonglong2*>(uB1 + trow + g);
+                            macc(t, a0.x, b1.x);
+                            macc(t, a1.x, b0.x);
+                            macc(t, c0.x, e1.x);
+                            macc(t, c1.x, e0.x);
+                            macc(u, a0.y, b1.y);
+                            macc(u, a1.y, b0.y);
+                            macc(u, c0.y, e1.y);
+                            macc(u, c1.y, e0.y);
+                        }
+                        o.x = sf_reduce128_acc(t.lo, t.hi, &EB);
+                        o.y = sf_reduce128_acc(u.lo, u.hi, &EB);
+                    } else if (pp == 0) {
                         o.x = bmul(a0.x, b0.x, EB);
                         o.y = bmul(a0.y, b0.y, EB);
                     } else {
@@ -1602,6 +1669,10 @@ struct KsArgs {
     // non-null: the fold rows are the tensor's d0 = a0 b0, d1 = a0 b1 + a1 b0
     // at row ell - 1, formed here (fold0 / fold1 unused)
     const u64 *fa0, *fa1, *fb0, *fb1;
+    // non-null (with fa0 and inMul): a second product summed with the first
+    // (sfp_mult2_relin_rescale_add) -- the own limbs are in (.) inMul + ga1 (.) gb1
+    // and the fold rows gain the second tensor's d0 / d1
+    const u64 *ga0, *ga1, *gb0, *gb1;
     uint32_t ell, Lq, alpha, beta;
     int accum;  // acc += the inner product
     // rows t >= invFrom (the P limbs, and for a ModDown fused with its rescale
@@ -1612,7 +1683,8 @@ struct KsArgs {
     const double* itwD;
 };
 
-template <int LE, int TILE, int NG = 1>
+// DOT: with the second product's rows (KsArgs::ga0 ..) compiled in, as k_ntt's
+template <int LE, int TILE, int NG = 1, bool DOT = false>
 __global__ __launch_bounds__(TILE >> LE) void k_ntt_ks(const ArgSet<KsArgs, NG> AS, const sf_barrett* __restrict__ bar,
                                                      const u64* __restrict__ tw, const u64* __restrict__ twS,
                                                      uint32_t logn, const double* __restrict__ twD,
@@ -1727,6 +1799,13 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt_ks(const ArgSet<KsArgs, NG> 
                         const ulonglong2 m = *reinterpret_cast<const ulonglong2*>(mul + e);
                         x.x = bmul(x.x, m.x, B);
                         x.y = bmul(x.y, m.y, B);
+                        if (DOT && A.ga1) {
+                            const size_t ro = (size_t)t * n + rowOff + e;
+                            const ulonglong2 x2 = *reinterpret_cast<const ulonglong2*>(A.ga1 + ro);
+                            const ulonglong2 m2 = *reinterpret_cast<const ulonglong2*>(A.gb1 + ro);
+                            x.x = sf_add(x.x, bmul(x2.x, m2.x, B), q);
+                            x.y = sf_add(x.y, bmul(x2.y, m2.y, B), q);
+                        }
                     }
                     if constexpr (FP) {
                         v[2 * k] = u2d(x.x);
@@ -1846,9 +1925,21 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt_ks(const ArgSet<KsArgs, NG> 
                         const double fk = u2d(A.foldK), fkq = fk * qi;
                         const double qx0 = u2d(x0.x), qy0 = u2d(x0.y), qx1 = u2d(x1.x), qy1 = u2d(x1.y);
                         const double b0x = u2d(y0.x), b0y = u2d(y0.y), b1x = u2d(y1.x), b1y = u2d(y1.y);
-                        const double f0x = fpMulMod(qx0, b0x, b0x * qi, qd), f0y = fpMulMod(qy0, b0y, b0y * qi, qd);
-                        const double f1x = fpMulMod(qx0, b1x, b1x * qi, qd) + fpMulMod(qx1, b0x, b0x * qi, qd);
-                        const double f1y = fpMulMod(qy0, b1y, b1y * qi, qd) + fpMulMod(qy1, b0y, b0y * qi, qd);
+                        double f0x = fpMulMod(qx0, b0x, b0x * qi, qd), f0y = fpMulMod(qy0, b0y, b0y * qi, qd);
+                        double f1x = fpMulMod(qx0, b1x, b1x * qi, qd) + fpMulMod(qx1, b0x, b0x * qi, qd);
+                        double f1y = fpMulMod(qy0, b1y, b1y * qi, qd) + fpMulMod(qy1, b0y, b0y * qi, qd);
+                        if (DOT && A.ga0) {  // (each term |r| < 2q: the sums stay far below fpMulMod's 2^52)
+                            const ulonglong2 z0 = *reinterpret_cast<const ulonglong2*>(A.ga0 + ro);
+                            const ulonglong2 z1 = *reinterpret_cast<const ulonglong2*>(A.ga1 + ro);
+                            const ulonglong2 w0 = *reinterpret_cast<const ulonglong2*>(A.gb0 + ro);
+                            const ulonglong2 w1 = *reinterpret_cast<const ulonglong2*>(A.gb1 + ro);
+                            const double cx0 = u2d(z0.x), cy0 = u2d(z0.y), cx1 = u2d(z1.x), cy1 = u2d(z1.y);
+                            const double e0x = u2d(w0.x), e0y = u2d(w0.y), e1x = u2d(w1.x), e1y = u2d(w1.y);
+                            f0x += fpMulMod(cx0, e0x, e0x * qi, qd);
+                            f0y += fpMulMod(cy0, e0y, e0y * qi, qd);
+                            f1x += fpMulMod(cx0, e1x, e1x * qi, qd) + fpMulMod(cx1, e0x, e0x * qi, qd);
+                            f1y += fpMulMod(cy0, e1y, e1y * qi, qd) + fpMulMod(cy1, e0y, e0y * qi, qd);
+                        }
                         a0[2 * k] += fpMulMod(f0x, fk, fkq, qd);
                         a0[2 * k + 1] += fpMulMod(f0y, fk, fkq, qd);
                         a1[2 * k] += fpMulMod(f1x, fk, fkq, qd);
@@ -1859,8 +1950,21 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt_ks(const ArgSet<KsArgs, NG> 
                         macc(tt, x1.x, y0.x);
                         macc(uu, x0.y, y1.y);
                         macc(uu, x1.y, y0.y);
-                        macc(a0[2 * k], bmul(x0.x, y0.x, B), A.foldK);
-                        macc(a0[2 * k + 1], bmul(x0.y, y0.y, B), A.foldK);
+                        u64 g0x = bmul(x0.x, y0.x, B), g0y = bmul(x0.y, y0.y, B);
+                        if (DOT && A.ga0) {
+                            const ulonglong2 z0 = *reinterpret_cast<const ulonglong2*>(A.ga0 + ro);
+                            const ulonglong2 z1 = *reinterpret_cast<const ulonglong2*>(A.ga1 + ro);
+                            const ulonglong2 w0 = *reinterpret_cast<const ulonglong2*>(A.gb0 + ro);
+                            const ulonglong2 w1 = *reinterpret_cast<const ulonglong2*>(A.gb1 + ro);
+                            macc(tt, z0.x, w1.x);
+                            macc(tt, z1.x, w0.x);
+                            macc(uu, z0.y, w1.y);
+                            macc(uu, z1.y, w0.y);
+                            g0x = sf_add(g0x, bmul(z0.x, w0.x, B), q);
+                            g0y = sf_add(g0y, bmul(z0.y, w0.y, B), q);
+                        }
+                        macc(a0[2 * k], g0x, A.foldK);
+                        macc(a0[2 * k + 1], g0y, A.foldK);
                         macc(a1[2 * k], sf_reduce128_acc(tt.lo, tt.hi, &B), A.foldK);
                         macc(a1[2 * k + 1], sf_reduce128_acc(uu.lo, uu.hi, &B), A.foldK);
                     }
@@ -4275,9 +4379,15 @@ static auto withWidth(int cnt, F&& f) {
 // -- "Cannot find Symbol" at launch.)
 using NttKerns = SetKerns<RowGroup, const sf_barrett*, const u64*, const u64*, const u64*, const u64*, uint32_t,
                           const double*, const double*, const double*, const double*, int, const double*>;
-template <bool INV, bool COL, int LE, int TILE, bool CONV = false>
+// (DOT, the two-product forms: one set or a merged pair -- the sort's two lanes)
+template <bool INV, bool COL, int LE, int TILE, bool CONV = false, bool DOT = false>
 static NttKerns nttKerns() {
-    if constexpr (LE == 2)
+    if constexpr (DOT && LE == 2)
+        return {k_ntt<INV, COL, LE, TILE, 1, CONV, true>, k_ntt<INV, COL, LE, TILE, 2, CONV, true>, nullptr, nullptr,
+                TILE, TILE >> LE};
+    else if constexpr (DOT)
+        return {k_ntt<INV, COL, LE, TILE, 1, CONV, true>, nullptr, nullptr, nullptr, TILE, TILE >> LE};
+    else if constexpr (LE == 2)
         return {k_ntt<INV, COL, LE, TILE, 1, CONV>, k_ntt<INV, COL, LE, TILE, 2, CONV>,
                 k_ntt<INV, COL, LE, TILE, 4, CONV>, k_ntt<INV, COL, LE, TILE, 8, CONV>, TILE, TILE >> LE};
     else  // (kNttSmallRows rows or more: never merged)
@@ -4295,9 +4405,13 @@ static NttKerns moddownColKerns() {
 }
 using KsKerns = SetKerns<KsArgs, const sf_barrett*, const u64*, const u64*, uint32_t, const double*, const double*,
                          int, const double*>;
-template <int TILE>
+template <int TILE, bool DOT = false>
 static KsKerns ksKerns() {
-    return {k_ntt_ks<2, TILE, 1>, k_ntt_ks<2, TILE, 2>, k_ntt_ks<2, TILE, 4>, k_ntt_ks<2, TILE, 8>, TILE, TILE >> 2};
+    if constexpr (DOT)
+        return {k_ntt_ks<2, TILE, 1, true>, k_ntt_ks<2, TILE, 2, true>, nullptr, nullptr, TILE, TILE >> 2};
+    else
+        return {k_ntt_ks<2, TILE, 1>, k_ntt_ks<2, TILE, 2>, k_ntt_ks<2, TILE, 4>, k_ntt_ks<2, TILE, 8>, TILE,
+                TILE >> 2};
 }
 // (four element-wise argument sets fill the 4 KB of kernel arguments: no k8)
 template <class A>
@@ -5300,7 +5414,7 @@ static void nttRows(sfp_dev* d, const RowGroup& G0, int inverse, int passes = 3)
     auto le2Passes = [&](auto tileC) {
         constexpr int TL = decltype(tileC)::value;
         if (inverse) {
-            pass(nttKerns<true, false, 2, TL>());
+            pass(G.t2 ? nttKerns<true, false, 2, TL, false, true>() : nttKerns<true, false, 2, TL>());
             pass(nttKerns<true, true, 2, TL>());
             return;
         }
@@ -5320,7 +5434,7 @@ static void nttRows(sfp_dev* d, const RowGroup& G0, int inverse, int passes = 3)
             pass(nttKerns<false, true, 2, TL>());
         }
         gridRows = rows;
-        pass(nttKerns<false, false, 2, TL>());
+        pass(G.t2 ? nttKerns<false, false, 2, TL, false, true>() : nttKerns<false, false, 2, TL>());
     };
     constexpr int T = kNttTile;
     if (t1k) {
@@ -5329,9 +5443,9 @@ static void nttRows(sfp_dev* d, const RowGroup& G0, int inverse, int passes = 3)
         le2Passes(std::integral_constant<int, T>{});
     } else if (!inverse) {  // kNttSmallRows rows or more: single-group LE = 3 kernels
         pass(nttKerns<false, true, 3, T>());
-        pass(nttKerns<false, false, 3, T>());
+        pass(G.t2 ? nttKerns<false, false, 3, T, false, true>() : nttKerns<false, false, 3, T>());
     } else {
-        pass(nttKerns<true, false, 3, T>());
+        pass(G.t2 ? nttKerns<true, false, 3, T, false, true>() : nttKerns<true, false, 3, T>());
         pass(nttKerns<true, true, 3, T>());
     }
     checkLaunch(d, "ntt");
@@ -5501,13 +5615,18 @@ static uint32_t kernelFamily(const void* f) {
                                       nttKerns<true, true, 2, TL>(), nttKerns<true, false, 2, TL>(),
                                       nttKerns<false, true, 2, TL, true>()})  // (the last: ModUp's COL pass with its conversion)
                 add(K, SFP_FAM_NTT);
+            add(nttKerns<false, false, 2, TL, false, true>(), SFP_FAM_NTT);  // (the two-product forms)
+            add(nttKerns<true, false, 2, TL, false, true>(), SFP_FAM_NTT);
             add(ksKerns<TL>(), SFP_FAM_NTTKS);
+            add(ksKerns<TL, true>(), SFP_FAM_NTTKS);
         };
         tile(std::integral_constant<int, kNttTile>{});
         tile(std::integral_constant<int, kNttSmallTile>{});
         for (const NttKerns& K : {nttKerns<false, true, 3, kNttTile>(), nttKerns<false, false, 3, kNttTile>(),
                                   nttKerns<true, true, 3, kNttTile>(), nttKerns<true, false, 3, kNttTile>()})
             add(K, SFP_FAM_NTT);
+        add(nttKerns<false, false, 3, kNttTile, false, true>(), SFP_FAM_NTT);
+        add(nttKerns<true, false, 3, kNttTile, false, true>(), SFP_FAM_NTT);
         for (bool md : {false, true})
             for (const NttKerns& K : fusedColKerns(md)) add(K, SFP_FAM_NTT);
         for (const void* k : {(const void*)k_convf<13>, (const void*)k_convf<16>, (const void*)k_convf<kMaxConvSrc>,
@@ -5585,7 +5704,9 @@ static double ksNodeBytesNG(const void* arg, uint32_t gridY, uint32_t n) {
 }
 static double ksNodeBytes(const hipKernelNodeParams& kp, uint32_t n) {
     if (!kp.kernelParams) return 0;
-    const int w = std::max(ksKerns<kNttSmallTile>().widthOf(kp.func), ksKerns<kNttTile>().widthOf(kp.func));
+    const int w = std::max(std::max(ksKerns<kNttSmallTile>().widthOf(kp.func), ksKerns<kNttTile>().widthOf(kp.func)),
+                           std::max(ksKerns<kNttSmallTile, true>().widthOf(kp.func),
+                                    ksKerns<kNttTile, true>().widthOf(kp.func)));
     return withWidth(w, [&](auto ng) { return ksNodeBytesNG<decltype(ng)::value>(kp.kernelParams[0], kp.gridDim.y, n); });
 }
 
@@ -6586,11 +6707,14 @@ static bool ksFuse() {  // SFHE_KS_FUSE=0: the unfused sequences (A/B)
 // INTT of the input (in, or in (.) inMul: a tensor's d2 = a1 b1 formed in the
 // first pass), the digits' conversions, the forward COL pass, then k_ntt_ks.
 // T[4] (a0, a1, b0, b1) non-null: the fold rows are the tensor's d0 / d1.
+// T2[4] (with T and inMul): a second product's rows, summed with the first's
+// wherever those are read (t2dev: their device copy for k_ntt).
 static void modupInnerCore(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_t* in, const uint64_t* inMul,
                            uint32_t ell, uint32_t K, uint32_t Lq, uint32_t alpha, const sfp_conv* const* convs,
                            const uint64_t* key, const uint64_t* fold0, const uint64_t* fold1,
                            const uint64_t* const* T, uint64_t foldK, int accum, uint32_t invFrom, uint64_t* ext,
-                           uint64_t* scr, int phases = 3) {
+                           uint64_t* scr, int phases = 3, const uint64_t* const* T2 = nullptr,
+                           const u64* const* t2dev = nullptr) {
     const uint32_t n = d->n;
     const uint32_t beta = (ell + alpha - 1) / alpha;
     const long long stride = (long long)(ell + K) * n;
@@ -6600,6 +6724,7 @@ static void modupInnerCore(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uin
     A.src = RowPtr{in, 0, (long long)n};
     A.dst = RowPtr{scr, 0, (long long)n};
     if (inMul) A.pre = RowPtr{inMul, 0, (long long)n};
+    if (inMul && T2) A.t2 = t2dev;
     RowGroup B = rowsOf(beta, ell + K, sfp_limbs{ell + K, ell, Lq, 0});
     B.src = B.dst = RowPtr{ext, stride, (long long)n};
     B.skipEll = ell;
@@ -6639,6 +6764,12 @@ static void modupInnerCore(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uin
         a.fa1 = T[1];
         a.fb0 = T[2];
         a.fb1 = T[3];
+        if (T2 && inMul) {
+            a.ga0 = T2[0];
+            a.ga1 = T2[1];
+            a.gb0 = T2[2];
+            a.gb1 = T2[3];
+        }
     }
     a.foldK = foldK;
     a.ell = ell;
@@ -6653,7 +6784,9 @@ static void modupInnerCore(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uin
     const uint32_t rows = ell + K;
     const size_t total = (size_t)rows * n;
     const KsArgs* pa = &a;
-    const KsKerns kerns = nttSmallTile(d, rows, kKsT1kRows) ? ksKerns<kNttSmallTile>() : ksKerns<kNttTile>();
+    const bool small = nttSmallTile(d, rows, kKsT1kRows);
+    const KsKerns kerns = a.ga0 ? (small ? ksKerns<kNttSmallTile, true>() : ksKerns<kNttTile, true>())
+                                : (small ? ksKerns<kNttSmallTile>() : ksKerns<kNttTile>());
     timedLaunch(d, SFP_FAM_NTTKS, 8.0 * total * (3.0 * beta + (accum ? 4.0 : 2.0)),
                 [&] { issueSets(d, STK_KS, kerns, &pa, &rows, 1, nttTables(d, 0)); });
     checkLaunch(d, "ntt_ks");
@@ -7017,7 +7150,8 @@ static void epiAddInto(sfp_dev* d, RowGroup& B, const EpiAdd& e, uint32_t npoly,
 static void moddownRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* d0, const uint64_t* d1,
                                const uint64_t* const* T, uint64_t* acc, size_t accStride, uint32_t ell, uint32_t K,
                                uint32_t Lq, const sfp_conv* c, const uint64_t* pinv, const uint64_t* pmod,
-                               const uint64_t* qlinv, uint64_t* scr, int rowDone, const EpiAdd& ea = EpiAdd{}) {
+                               const uint64_t* qlinv, uint64_t* scr, int rowDone, const EpiAdd& ea = EpiAdd{},
+                               const u64* const* t2dev = nullptr) {
     const uint32_t n = d->n, l = ell - 1;
     if (ell < 2 || ell > SFP_MAX_LIMBS || !c || c->ns > (uint32_t)kMaxConvSrc || c->nt < ell ||
         !limbsOk(d, sfp_limbs{K + 1, 1, Lq, l}, "moddown_rescale")) {
@@ -7139,6 +7273,7 @@ static void moddownRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, const
         B.tA1 = T[1];
         B.tB0 = T[2];
         B.tB1 = T[3];
+        B.t2 = t2dev;  // (a second product's rows: the tensor is the sum of both)
     } else {
         B.eadd = RowPtr{d0, (long long)(d1 - d0), (long long)n};
     }
@@ -7162,7 +7297,7 @@ static int multRelinRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, cons
                                 const uint64_t* b0, const uint64_t* b1, uint32_t ell, uint32_t K, uint32_t Lq,
                                 uint32_t alpha, const sfp_conv* const* convs, const uint64_t* key, const sfp_conv* c,
                                 const uint64_t* pinv, const uint64_t* pmod, const uint64_t* qlinv, uint64_t* acc,
-                                uint64_t* ext, uint64_t* scr, const EpiAdd& ea) {
+                                uint64_t* ext, uint64_t* scr, const EpiAdd& ea, const uint64_t* const* T2 = nullptr) {
     const uint32_t beta = (ell + alpha - 1) / alpha;
     if (!ksFuse() || d->n <= (uint32_t)kNttTile) return -1;
     if (ell < 2 || beta > (uint32_t)kMaxConvJobs || ell + K > SFP_MAX_LIMBS) {
@@ -7170,12 +7305,20 @@ static int multRelinRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, cons
         return 0;
     }
     const uint64_t* T[4] = {a0, a1, b0, b1};
+    // the second product's row bases, where k_ntt's argument block has one pointer for them
+    const u64* const* t2dev = nullptr;
+    if (T2) {
+        u64 w[4];
+        for (int i = 0; i < 4; ++i) w[i] = (u64)(uintptr_t)T2[i];
+        t2dev = reinterpret_cast<const u64* const*>(devConst(d, w, 4));
+        if (!t2dev) return 0;  // (recorded)
+    }
     // d2 = a1 b1 in the ModUp's first pass and the own digits; d0, d1 at row
     // ell - 1 in the inner product's fold, the rest in the ModDown's epilogue
     modupInnerCore(d, acc, acc + (size_t)(ell + K) * d->n, a1, b1, ell, K, Lq, alpha, convs, key, nullptr, nullptr,
-                   T, pmod[ell - 1], 0, ell - 1, ext, scr);
+                   T, pmod[ell - 1], 0, ell - 1, ext, scr, 3, T2, t2dev);
     moddownRescaleCore(d, out0, out1, nullptr, nullptr, T, acc, (size_t)(ell + K) * d->n, ell, K, Lq, c, pinv, pmod,
-                       qlinv, scr, 1, ea);
+                       qlinv, scr, 1, ea, t2dev);
     return 0;
 }
 
@@ -7208,6 +7351,24 @@ int sfp_mult_relin_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, const
     if (ell < 2 || ell > SFP_MAX_LIMBS) return -1;
     return multRelinRescaleCore(d, out0, out1, a0, a1, b0, b1, ell, K, Lq, alpha, convs, key, c, pinv, pmod, qlinv,
                                 acc, ext, scr, EpiAdd{r0, r1, sign, cstBoth(cst, ell - 1, kb)});
+}
+
+int sfp_mult2_relin_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* a0, const uint64_t* a1,
+                                const uint64_t* b0, const uint64_t* b1, const uint64_t* c0, const uint64_t* c1,
+                                const uint64_t* e0, const uint64_t* e1, uint32_t ell, uint32_t K, uint32_t Lq,
+                                uint32_t alpha, const sfp_conv* const* convs, const uint64_t* key, const sfp_conv* c,
+                                const uint64_t* pinv, const uint64_t* pmod, const uint64_t* qlinv, uint64_t* acc,
+                                uint64_t* ext, uint64_t* scr, const uint64_t* r0, const uint64_t* r1, int sign,
+                                const uint64_t* cst) {
+    uint64_t kb[2 * SFP_MAX_LIMBS];
+    if (ell < 2 || ell > SFP_MAX_LIMBS) return -1;
+    // declined (nothing done): a missing row set, rows the 16-byte accesses cannot take
+    const uintptr_t bits = (uintptr_t)a0 | (uintptr_t)a1 | (uintptr_t)b0 | (uintptr_t)b1 | (uintptr_t)c0 |
+                           (uintptr_t)c1 | (uintptr_t)e0 | (uintptr_t)e1;
+    if (!a0 || !a1 || !b0 || !b1 || !c0 || !c1 || !e0 || !e1 || (bits & 15)) return -1;
+    const uint64_t* T2[4] = {c0, c1, e0, e1};
+    return multRelinRescaleCore(d, out0, out1, a0, a1, b0, b1, ell, K, Lq, alpha, convs, key, c, pinv, pmod, qlinv,
+                                acc, ext, scr, EpiAdd{r0, r1, sign, cstBoth(cst, ell - 1, kb)}, T2);
 }
 
 int sfp_moddown_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* d0, const uint64_t* d1,

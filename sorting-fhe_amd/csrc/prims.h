@@ -338,6 +338,28 @@ SFP_OPTIONAL int sfp_mul_const_rescale_add(sfp_dev* d, uint64_t* out, const uint
                                            uint32_t ell, const uint64_t* qlinv, uint32_t npoly, size_t in_stride,
                                            size_t out_stride, const uint64_t* cst);
 
+// ---- optional: the sum of two products relinearised once ------------------------
+// out = Rescale(Relin(a (x) b + a' (x) b')) (+- r, + cst): with
+//   d0 = a0 b0 + a0' b0',  d1 = a0 b1 + a1 b0 + a0' b1' + a1' b0',  d2 = a1 b1 + a1' b1'
+// (each the canonical residue of the sum of the two tensors' canonical
+// components: sfp_tensor twice, then sfp_add per component) the integers of
+// sfp_modup + sfp_ks_inner_fold (fold_k = pmod[ell-1]) + sfp_moddown_rescale on
+// (d0, d1, d2), then the sum of sfp_mult_relin_rescale_add.  The launch chain
+// is that of sfp_mult_relin_rescale: the second operand set is read where the
+// first is (the ModUp's first pass and own digits, the fold at row ell - 1,
+// the last pass's epilogue); no component is written out.  Arguments as
+// sfp_mult_relin_rescale_add; (c0, c1), (e0, e1): the second pair's rows.
+// Weak like the prims above: where its address is null (the C oracle) or it
+// returns -1 (no fused form here, nothing done) the host layer composes it.
+SFP_OPTIONAL int sfp_mult2_relin_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* a0,
+                                             const uint64_t* a1, const uint64_t* b0, const uint64_t* b1,
+                                             const uint64_t* c0, const uint64_t* c1, const uint64_t* e0,
+                                             const uint64_t* e1, uint32_t ell, uint32_t K, uint32_t Lq, uint32_t alpha,
+                                             const sfp_conv* const* convs, const uint64_t* key, const sfp_conv* c,
+                                             const uint64_t* pinv, const uint64_t* pmod, const uint64_t* qlinv,
+                                             uint64_t* acc, uint64_t* ext, uint64_t* scratch, const uint64_t* r0,
+                                             const uint64_t* r1, int sign, const uint64_t* cst);
+
 // ---- optional: several constant rescales of one input in one launch pair per direction
 // Term j of m (2 <= m <= SFP_MAX_CONST_TERMS) is sfp_mul_const_rescale(_add)
 // of the input's first ell_j rows: out_j = Rescale(in * k_j) (+ cst_j), k_j

@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "sfhe_sorter_select_many", "sfhe_sorter_select_records", "sfhe_eval_rotate_fold_many", "sfhe_select_cols_counts",
     "sfhe_lex_sort_depth", "sfhe_sorter_rank_lex", "sfhe_sorter_sort_records_lex", "sfhe_sorter_select_records_lex",
     "sfhe_eval_lex_step", "sfhe_lex_counts",
+    "sfhe_eval_mult_sum2", "sfhe_dot_counts",
 ]
 
 MAX_COLUMNS = 8  # SFHE_MAX_COLUMNS
@@ -209,6 +210,8 @@ _SIGS = {
                                                  C.c_int, C.c_int, _PVP, _PVP]),
     "sfhe_eval_lex_step": (C.c_int, [_VP, _VP, _VP, _VP, _PVP]),
     "sfhe_lex_counts": (C.c_int, [_VP, _PU64, _PU64]),
+    "sfhe_eval_mult_sum2": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _PVP]),
+    "sfhe_dot_counts": (C.c_int, [_VP, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -527,6 +530,17 @@ class Engine:
         """v + (1 - q) * u, one level below u (one relinearisation, one rescale): the
         lexicographic rank's Horner step.  v and q may sit at a numerically lower level than u."""
         return self._new(self.lib.sfhe_eval_lex_step, self.ctx, v.h, q.h, u.h)
+
+    def mult_sum2(self, a, b, a2, b2, r=None):
+        """a*b + a2*b2 (+ r), one level below the operands, from ONE relinearisation and
+        rescale (operands at one level; r, if given, at the result's level)."""
+        return self._new(self.lib.sfhe_eval_mult_sum2, self.ctx, a.h, b.h, a2.h, b2.h, r.h if r is not None else None)
+
+    def dot_counts(self):
+        """(fused, composed) mult_sum2 calls (the sign polynomials' included) since the last op_stats reset."""
+        f, c = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_dot_counts(self.ctx, C.byref(f), C.byref(c)))
+        return f.value, c.value
 
     def lex_counts(self):
         """(fused, composed) lex_step tensors (rank_lex's included) since the last op_stats reset."""
