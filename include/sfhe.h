@@ -39,7 +39,9 @@ extern "C" {
  * several keys: SFHE_LEX_KEYS, sfhe_lex_sort_depth, sfhe_sorter_rank_lex,
  * sfhe_sorter_sort_records_lex, sfhe_sorter_select_records_lex,
  * sfhe_eval_lex_step, sfhe_lex_counts, and the sum of two products:
- * sfhe_eval_mult_sum2, sfhe_dot_counts) */
+ * sfhe_eval_mult_sum2, sfhe_dot_counts, and the sum of n products:
+ * sfhe_eval_mult_sum, sfhe_eval_mult_sum_many, sfhe_sumn_counts,
+ * sfhe_sumn_batch_counts, sfhe_ct_relabel_scale) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -407,6 +409,32 @@ int sfhe_lex_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
 int sfhe_eval_mult_sum2(sfhe_ctx* c, const sfhe_ct* a, const sfhe_ct* b, const sfhe_ct* a2, const sfhe_ct* b2,
                         const sfhe_ct* r, sfhe_ct** out);
 int sfhe_dot_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
+/* Rescale(Relin(sum_i a[i] (x) b[i])) + r for 1 <= n <= 8 terms, one level below
+ * the operands: sfhe_eval_mult_sum2's contract with n pairs (all 2n operands
+ * at one level, equal product scales; r: null, or a ciphertext at the result's
+ * level).  The Chebyshev evaluator's remainder chains run through it
+ * (SFHE_PS_DOT=0, read per call, keeps one product per node).
+ * sfhe_sumn_counts: such sums that ran as one fused launch chain
+ * (sfp_multn_relin_rescale_add) and as the composed generic prims since the
+ * last sfhe_op_stats reset (SFHE_MULT_SUM_FUSED=0, read per call, composes;
+ * the results are bit-identical); sfhe_eval_mult_sum2's are not included. */
+int sfhe_eval_mult_sum(sfhe_ctx* c, const sfhe_ct* const* a, const sfhe_ct* const* b, size_t n, const sfhe_ct* r,
+                       sfhe_ct** out);
+int sfhe_sumn_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
+/* nops independent sfhe_eval_mult_sum ops in one call (EvalMultSumMany): op o
+ * has counts[o] terms, the terms of all ops laid end to end in a / b; r: null,
+ * or nops addends (null entries allowed); out: nops handles.  Consecutive ops
+ * of one level and one term count go out as one batch, ops of different term
+ * counts never share one; each result equals the op issued alone.
+ * sfhe_sumn_batch_counts: such runs issued, and remainder chains of the
+ * Chebyshev evaluator that fell outside the op's conditions and ran as
+ * separate products, since the last sfhe_op_stats reset. */
+int sfhe_eval_mult_sum_many(sfhe_ctx* c, const sfhe_ct* const* a, const sfhe_ct* const* b, const size_t* counts,
+                            size_t nops, const sfhe_ct* const* r, sfhe_ct** out);
+int sfhe_sumn_batch_counts(sfhe_ctx* c, uint64_t* batches, uint64_t* fallbacks);
+/* A copy of ct whose scale label is multiplied by factor (the rows are not
+ * touched): for testing how the evaluator treats operands of unequal scales. */
+int sfhe_ct_relabel_scale(const sfhe_ct* ct, double factor, sfhe_ct** out);
 /* nodes of the captured record sort (0 while none); sfhe_sorter_graph_nodes
  * keeps reporting the plain / stable sort's graph */
 int sfhe_sorter_records_graph_nodes(const sfhe_sorter* s, uint64_t* nodes);

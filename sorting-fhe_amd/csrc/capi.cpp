@@ -439,6 +439,22 @@ int sfhe_dot_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
     return SFHE_OK;
 }
 
+int sfhe_sumn_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
+    REQUIRE(c && fused && composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *fused = s.sumn_fused;
+    *composed = s.sumn_composed;
+    return SFHE_OK;
+}
+
+int sfhe_sumn_batch_counts(sfhe_ctx* c, uint64_t* batches, uint64_t* fallbacks) {
+    REQUIRE(c && batches && fallbacks, "null argument");
+    auto s = c->cc->GetOpStats();
+    *batches = s.sumn_batches;
+    *fallbacks = s.sumn_fallbacks;
+    return SFHE_OK;
+}
+
 int sfhe_place_counts(sfhe_ctx* c, uint64_t* hits, uint64_t* columns, uint64_t* fused, uint64_t* composed) {
     REQUIRE(c && hits && columns && fused && composed, "null argument");
     auto s = c->cc->GetOpStats();
@@ -888,6 +904,65 @@ int sfhe_eval_mult_sum2(sfhe_ctx* c, const sfhe_ct* a, const sfhe_ct* b, const s
         for (const sfhe_ct* x : {a, b, a2, b2, r})
             if (x) c->cc->Settle(x->ct);
         *out = wrap(c->cc->EvalMultSum2(a->ct, b->ct, a2->ct, b2->ct, r ? r->ct : nullptr));
+    });
+}
+
+int sfhe_eval_mult_sum(sfhe_ctx* c, const sfhe_ct* const* a, const sfhe_ct* const* b, size_t n, const sfhe_ct* r,
+                       sfhe_ct** out) {
+    REQUIRE(c && a && b && out, "null argument");
+    REQUIRE(n >= 1, "no terms");
+    for (size_t i = 0; i < n; ++i) REQUIRE(a[i] && b[i], "null term");
+    return guard([&] {
+        std::vector<lbcrypto::CryptoContextImpl<lbcrypto::DCRTPoly>::MultTerm> terms;
+        for (size_t i = 0; i < n; ++i) {
+            c->cc->Settle(a[i]->ct);
+            c->cc->Settle(b[i]->ct);
+            terms.emplace_back(a[i]->ct, b[i]->ct);
+        }
+        lbcrypto::CryptoContextImpl<lbcrypto::DCRTPoly>::MultAddend add;
+        if (r) {
+            c->cc->Settle(r->ct);
+            add.r = r->ct;
+        }
+        *out = wrap(c->cc->EvalMultSum(terms, add));
+    });
+}
+
+int sfhe_eval_mult_sum_many(sfhe_ctx* c, const sfhe_ct* const* a, const sfhe_ct* const* b, const size_t* counts,
+                            size_t nops, const sfhe_ct* const* r, sfhe_ct** out) {
+    REQUIRE(c && a && b && counts && out, "null argument");
+    size_t total = 0;
+    for (size_t o = 0; o < nops; ++o) {
+        REQUIRE(counts[o] >= 1, "an op without terms");
+        total += counts[o];
+    }
+    for (size_t i = 0; i < total; ++i) REQUIRE(a[i] && b[i], "null term");
+    return guard([&] {
+        using CC = lbcrypto::CryptoContextImpl<lbcrypto::DCRTPoly>;
+        std::vector<CC::MultSumOp> ops(nops);
+        size_t at = 0;
+        for (size_t o = 0; o < nops; ++o) {
+            for (size_t k = 0; k < counts[o]; ++k, ++at) {
+                c->cc->Settle(a[at]->ct);
+                c->cc->Settle(b[at]->ct);
+                ops[o].terms.emplace_back(a[at]->ct, b[at]->ct);
+            }
+            if (r && r[o]) {
+                c->cc->Settle(r[o]->ct);
+                ops[o].add.r = r[o]->ct;
+            }
+        }
+        auto res = c->cc->EvalMultSumMany(ops);
+        for (size_t o = 0; o < nops; ++o) out[o] = wrap(res[o]);
+    });
+}
+
+int sfhe_ct_relabel_scale(const sfhe_ct* ct, double factor, sfhe_ct** out) {
+    REQUIRE(ct && out, "null argument");
+    return guard([&] {
+        auto x = ct->ct->Clone();
+        x->scale *= factor;
+        *out = wrap(x);
     });
 }
 

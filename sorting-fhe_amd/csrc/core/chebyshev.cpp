@@ -85,7 +85,36 @@ bool psWaves() {
     return on;
 }
 
+// SFHE_PS_DOT=0 (read per call): every node of a remainder chain takes a
+// product chain of its own (the route before EvalMultSum).  Otherwise a node
+// p = q T_M + r whose r is again a node q' T_M' + r' with a ciphertext quotient
+// at the same product level absorbs it, and so on down the chain up to
+// kSpineCap terms: p = q T_M + q' T_M' + ... + tail is ONE EvalMultSum (one
+// relinearisation, ModDown and rescale) with the tail as its addend.  The rule
+// reads the tree alone, so both evaluation orders pair the same nodes.
+bool psDot() {
+    const char* v = std::getenv("SFHE_PS_DOT");
+    const char* nat = std::getenv("SFHE_PS_NATURAL");  // (natural levels: a chain's operands at several levels)
+    return !(v && *v == '0') && !(nat && *nat == '1');
+}
+constexpr size_t kSpineCap = 6;  // (the N = 256 doubled sinc's longest chain)
+static_assert(kSpineCap <= CryptoContextImpl<DCRTPoly>::kMultSumMaxTerms, "a chain longer than EvalMultSum takes");
+// SFHE_PS_DOT_CAP=c (read per call, 2 <= c <= kSpineCap): a lower cap (A/B knob: longer chains split)
+size_t spineCap() {
+    const char* v = std::getenv("SFHE_PS_DOT_CAP");
+    const long c = v ? std::atol(v) : 0;
+    return c >= 2 && c <= (long)kSpineCap ? (size_t)c : kSpineCap;
+}
+
 class PSEvaluator {
+    using Term = CryptoContextImpl<DCRTPoly>::MultTerm;
+    using SumOp = CryptoContextImpl<DCRTPoly>::MultSumOp;
+    // a node's division, as eval() / build() / plan() form it
+    struct Step {
+        uint32_t M = 0, Lp = 0, depth = 0;
+        std::vector<double> q, r;
+    };
+
   public:
     PSEvaluator(CryptoContextImpl<DCRTPoly>* cc, const Ct& y, uint32_t l, uint32_t D)
         : cc(cc), l(l), k(1u << l), D(D) {
@@ -216,6 +245,49 @@ class PSEvaluator {
         divide(p, M, q, r);
         const uint32_t Lp = productLevel(q, depth, M, want);
         const int half = span / 2;
+        if (psDot() && !constant(q)) {
+            // the remainder chain below this node (build()'s fuse(): the same rule);
+            // with lanes the head's own quotient goes to lane + span/2, the rest stays
+            const int sub = half ? half : 1;
+            std::vector<Term> terms;
+            Step cur{M, Lp, depth, q, r};
+            Val tail;
+            for (;;) {
+                const bool away = half && terms.empty();
+                if (away) cc->SetLane(lane + half);
+                Val qv = eval(cur.q, cur.depth - 1, Lp - 1, away ? lane + half : lane, sub);
+                if (away) cc->SetLane(lane);
+                terms.emplace_back(qv.ct, alignedPower(cur.M, Lp - 1));
+                Step nx;
+                if (terms.size() < spineCap() && split(cur.r, cur.depth, Lp, nx) && !constant(nx.q) && nx.Lp == Lp) {
+                    cur = std::move(nx);
+                    continue;
+                }
+                tail = eval(cur.r, cur.depth, Lp, lane, sub);
+                break;
+            }
+            if (terms.size() > 1) {
+                Val out;
+                out.isConst = false;
+                out.ct = spineSum({SumOp{terms, tail.isConst ? Addend{nullptr, 1, tail.c} : Addend{tail.ct, 1, 0.0}}})[0];
+                return out;
+            }
+            // a chain of one term: the product with its sum, as without the rule
+            Val out;
+            out.isConst = false;
+            const Addend add = tail.isConst ? Addend{nullptr, 1, tail.c} : Addend{tail.ct, 1, 0.0};
+            if (psFma()) {
+                out.ct = cc->EvalMultAdd(terms[0].first, terms[0].second, add);
+            } else {
+                out.ct = cc->EvalMult(terms[0].first, terms[0].second);
+                if (tail.isConst) {
+                    if (tail.c != 0.0) out.ct = cc->EvalAdd(out.ct, tail.c);
+                } else {
+                    out.ct = cc->EvalAdd(out.ct, tail.ct);
+                }
+            }
+            return out;
+        }
         if (half) cc->SetLane(lane + half);
         Val qv = eval(q, depth - 1, Lp - 1, half ? lane + half : lane, half ? half : 1);
         const Ct& TM = alignedPower(M, Lp - 1);
@@ -281,15 +353,78 @@ class PSEvaluator {
         return v;
     }
 
+    // The remainder chains (psDot): from the root down, a head takes the
+    // nodes of its r chain that eval() would take -- a ciphertext quotient, the
+    // head's product level, up to kSpineCap terms -- and the last one's r as its
+    // own; the quotients of all and that r are heads in turn.
+    void fuse(int root) {
+        std::vector<int> heads{root};
+        const size_t cap = spineCap();
+        while (!heads.empty()) {
+            const int h = heads.back();
+            heads.pop_back();
+            int cur = h;
+            if (!nodes[h].q.isConst)
+                while (1 + nodes[h].extra.size() < cap) {
+                    const int c = nodes[cur].r.node;
+                    if (c < 0 || nodes[c].q.isConst || nodes[c].Lp != nodes[h].Lp) break;
+                    nodes[h].extra.push_back(c);
+                    nodes[c].absorbed = true;
+                    cur = c;
+                }
+            if (nodes[h].q.node >= 0) heads.push_back(nodes[h].q.node);
+            for (int c : nodes[h].extra)
+                if (nodes[c].q.node >= 0) heads.push_back(nodes[c].q.node);
+            nodes[h].r = nodes[cur].r;
+            if (nodes[h].r.node >= 0) heads.push_back(nodes[h].r.node);
+        }
+    }
+
     Val run(const Val& root) {
         if (root.node < 0) return root;
+        if (psDot()) fuse(root.node);
         auto ready = [&](const Val& v) { return v.isConst || v.node < 0 || nodes[v.node].hasOut; };
         auto value = [&](const Val& v) -> const Ct& { return v.node < 0 ? v.ct : nodes[v.node].out; };
         while (!nodes[root.node].hasOut) {
             bool progress = false;
             std::map<std::pair<uint32_t, uint32_t>, std::vector<size_t>> waves;  // (M, Lp) -> nodes
-            for (size_t i = 0; i < nodes.size(); ++i)
-                if (!nodes[i].hasProd && ready(nodes[i].q)) waves[{nodes[i].M, nodes[i].Lp}].push_back(i);
+            std::map<std::pair<uint32_t, size_t>, std::vector<size_t>> chains;   // (Lp, terms) -> heads
+            for (size_t i = 0; i < nodes.size(); ++i) {
+                if (nodes[i].hasProd || nodes[i].absorbed || !ready(nodes[i].q)) continue;
+                if (nodes[i].extra.empty()) {
+                    waves[{nodes[i].M, nodes[i].Lp}].push_back(i);
+                    continue;
+                }
+                bool all = true;  // a head goes once every term's quotient is ready
+                for (int c : nodes[i].extra) all = all && ready(nodes[c].q);
+                if (all) chains[{nodes[i].Lp, 1 + nodes[i].extra.size()}].push_back(i);
+            }
+            for (auto& w : chains) {
+                const uint32_t Lp = w.first.first;
+                std::vector<SumOp> ops;
+                for (size_t i : w.second) {
+                    Node& nd = nodes[i];
+                    SumOp op;
+                    op.terms.emplace_back(value(nd.q), alignedPower(nd.M, Lp - 1));
+                    for (int c : nd.extra) op.terms.emplace_back(value(nodes[c].q), alignedPower(nodes[c].M, Lp - 1));
+                    const bool fold = ready(nd.r);  // (never waited for, as a single product's sum)
+                    if (fold) op.add = nd.r.isConst ? Addend{nullptr, 1, nd.r.c} : Addend{value(nd.r), 1, 0.0};
+                    nd.sumInProd = fold;
+                    ops.push_back(std::move(op));
+                }
+                auto sums = spineSum(ops);
+                for (size_t t = 0; t < w.second.size(); ++t) {
+                    Node& nd = nodes[w.second[t]];
+                    nd.hasProd = true;
+                    if (nd.sumInProd) {
+                        nd.out = sums[t];
+                        nd.hasOut = true;
+                    } else {
+                        nd.prod = sums[t];
+                    }
+                }
+                progress = true;
+            }
             for (auto& w : waves) {
                 const Ct& TM = alignedPower(w.first.first, w.first.second - 1);
                 std::vector<Ct> as, bs;
@@ -327,7 +462,7 @@ class PSEvaluator {
             // the ready sums, as batches of independent ops
             std::vector<Node*> sums;
             for (auto& nd : nodes)
-                if (!nd.hasOut && nd.hasProd && ready(nd.r)) sums.push_back(&nd);
+                if (!nd.hasOut && nd.hasProd && !nd.absorbed && ready(nd.r)) sums.push_back(&nd);
             for (size_t b0 = 0; b0 < sums.size(); b0 += batchWidth()) {
                 const size_t b1 = std::min(sums.size(), b0 + batchWidth());
                 BatchScope bs(cc, (uint32_t)(b1 - b0));
@@ -352,14 +487,74 @@ class PSEvaluator {
         return out;
     }
 
+    uint64_t fallbacks = 0;  // chains spineSum ran as separate products (OpStats sumn_fallbacks)
+
   private:
     struct Node {
         Val q, r;
         uint32_t M = 0, Lp = 0;
         Ct prod, out;
         bool hasProd = false, hasOut = false, sumInProd = false;
+        std::vector<int> extra;  // a chain's head: the nodes whose terms it took (fuse)
+        bool absorbed = false;   // ... and such a node: it has no product or value of its own
     };
     std::vector<Node> nodes;
+
+    // Is p a node (eval()'s control flow)?  Then st is its division at `want`.
+    bool split(std::vector<double> p, uint32_t depth, uint32_t want, Step& st) const {
+        trim(p);
+        if (p.size() <= 1) return false;
+        const uint32_t deg = (uint32_t)p.size() - 1;
+        if (deg <= k) return false;
+        while (depth >= 1 && deg + (1u << l) <= (1u << (depth - 1))) --depth;
+        st.M = deg >= (1u << (depth - 1)) ? (1u << (depth - 1)) : (1u << (depth - 2));
+        divide(p, st.M, st.q, st.r);
+        st.Lp = productLevel(st.q, depth, st.M, want);
+        st.depth = depth;
+        return true;
+    }
+
+    // a quotient that evaluates to a constant (no term of degree >= 1)
+    static bool constant(std::vector<double> q) {
+        trim(q);
+        return q.size() <= 1;
+    }
+
+    // The chains' sums: ops of one (product level, term count) as one
+    // EvalMultSumMany.  An op outside EvalMultSum's conditions (operands the
+    // tree did not bring to one level and scale) runs as its separate
+    // products and sums -- in both evaluation orders, so they still agree.
+    std::vector<Ct> spineSum(const std::vector<SumOp>& ops) {
+        std::vector<Ct> out(ops.size());
+        std::vector<SumOp> good;
+        std::vector<size_t> at;
+        for (size_t i = 0; i < ops.size(); ++i) {
+            for (const Term& t : ops[i].terms) {
+                cc->Settle(t.first);
+                cc->Settle(t.second);
+            }
+            if (ops[i].add.r) cc->Settle(ops[i].add.r);
+            if (!cc->MultSumViolation(ops[i])) {
+                good.push_back(ops[i]);
+                at.push_back(i);
+                continue;
+            }
+            ++fallbacks;
+            Ct v;
+            for (const Term& t : ops[i].terms) {
+                Ct pr = cc->EvalMult(t.first, t.second);
+                v = v ? cc->EvalAdd(v, pr) : pr;
+            }
+            if (ops[i].add.r) v = cc->EvalAdd(v, ops[i].add.r);
+            if (ops[i].add.c != 0.0) v = cc->EvalAdd(v, ops[i].add.c);
+            out[i] = v;
+        }
+        if (!good.empty()) {
+            auto r = cc->EvalMultSumMany(good);
+            for (size_t i = 0; i < at.size(); ++i) out[at[i]] = r[i];
+        }
+        return out;
+    }
 
     // p = q T_M + r (Chebyshev division by T_M, M >= deg / 2)
     static void divide(const std::vector<double>& p, uint32_t M, std::vector<double>& q, std::vector<double>& r) {
@@ -543,6 +738,10 @@ void psDebugCounts(const CryptoContextImpl<DCRTPoly>* cc, const char* where) {
     cc->FusedSumCounts(&sums, &consts, &pairs);
     std::fprintf(stderr, "PSFMA %s | fused sums %llu | fused constants %llu | paired weighted sums %llu\n", where,
                  (unsigned long long)sums, (unsigned long long)consts, (unsigned long long)pairs);
+    const auto st = cc->GetOpStats();
+    std::fprintf(stderr, "PSDOT %s | chains fused %llu | composed %llu | batches %llu | fell back %llu\n", where,
+                 (unsigned long long)st.sumn_fused, (unsigned long long)st.sumn_composed,
+                 (unsigned long long)st.sumn_batches, (unsigned long long)st.sumn_fallbacks);
 }
 
 }  // namespace
@@ -631,6 +830,7 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalChebyshevSeriesPS(
         if (batched) ps.precomputeLeaves(p, D);
         auto v = (lanes == 1 && psWaves()) ? ps.run(ps.build(p, D)) : ps.eval(p, D, 0, 0, lanes);
         out = v.isConst ? EvalAdd(EvalMult(y, 0.0), v.c) : v.ct;
+        st->stats.sumn_fallbacks += ps.fallbacks;
     }
     const uint32_t target = y->GetLevel() + D;
     if (out->GetLevel() > target)

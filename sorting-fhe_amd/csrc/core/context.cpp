@@ -3550,6 +3550,135 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMultSum2(const Ciphertext<
     return SfheInternal::traced(this, out, "EvalMultSum2");
 }
 
+// The sum of m products at one level, relinearised and rescaled once.
+Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMultSum(const std::vector<MultTerm>& terms,
+                                                             const MultAddend& add) {
+    return EvalMultSumMany({MultSumOp{terms, add}})[0];
+}
+
+const char* CryptoContextImpl<DCRTPoly>::MultSumViolation(const MultSumOp& op) const {
+    const SfheContextState* s = st.get();
+    const auto& T = op.terms;
+    const auto& r = op.add.r;
+    if (T.empty() || T.size() > kMultSumMaxTerms) return "the number of terms is outside 1 .. kMultSumMaxTerms";
+    for (const MultTerm& t : T) {
+        if (!t.first || !t.second) return "null operand";
+        if (SfheInternal::isLazy(t.first) || SfheInternal::isLazy(t.second))
+            return "an operand is a deferred or pending product (Settle it first)";
+    }
+    if (r && SfheInternal::isLazy(r)) return "the addend is a deferred or pending product (Settle it first)";
+    const uint32_t level = T[0].first->level;
+    const double sc = T[0].first->scale * T[0].second->scale;
+    for (const MultTerm& t : T) {
+        if (t.first->level != level || t.second->level != level)
+            return "the operands are at different levels (one level is required)";
+        if (t.first->scale * t.second->scale != sc) return "the products carry different scales";
+    }
+    if (s->ellOf(level) < 2 || level + 1 > s->L) return "no levels left (multiplicative depth exhausted)";
+    if (r && (r->level != level + 1 || r->scale != s->scale[level + 1]))
+        return "the addend is not canonical at the result's level";
+    return nullptr;
+}
+
+std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultSumMany(const std::vector<MultSumOp>& ops) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalMultSum");
+    const size_t cnt = ops.size();
+    const uint32_t n = s->n;
+    std::vector<Ciphertext<DCRTPoly>> out(cnt);
+    std::vector<uint32_t> slots(cnt);
+    for (size_t o = 0; o < cnt; ++o) {
+        if (const char* why = MultSumViolation(ops[o])) SFHE_THROW(std::string("EvalMultSum: ") + why);
+        slots[o] = ops[o].add.r ? ops[o].add.r->slots : 0;
+        for (const MultTerm& t : ops[o].terms)
+            slots[o] = std::max(slots[o], std::max(t.first->slots, t.second->slots));
+    }
+    for (size_t o = 0; o < cnt; ++o) {
+        for (const MultTerm& t : ops[o].terms) SfheInternal::deps(s, {&t.first, &t.second});
+        SfheInternal::deps(s, {&ops[o].add.r});
+        const size_t m = ops[o].terms.size();
+        s->stats.tensor += m;
+        s->countBytes(m * 7.0 * s->ellOf(ops[o].terms[0].first->level) * n * 8);
+    }
+    const char* knob = std::getenv("SFHE_MULT_SUM_FUSED");  // (read per call: tests switch it)
+    const bool fusedOn = sfp_multn_relin_rescale_add && !(knob && *knob == '0') && SfheInternal::fusedRescale();
+    // runs of up to BatchWidth() consecutive ops of one level and one term count
+    for (size_t i = 0; i < cnt;) {
+        const uint32_t level = ops[i].terms[0].first->level, ell = s->ellOf(level);
+        const size_t m = ops[i].terms.size();
+        size_t j = i + 1;
+        while (j < cnt && j - i < batchWidth() && ops[j].terms[0].first->level == level && ops[j].terms.size() == m) ++j;
+        const size_t pw = s->polyWords(level);
+        size_t done = i;
+        s->stats.sumn_batches++;
+        if (fusedOn && !s->shardAt(ell)) {
+            const DeviceBufferPtr& key = s->relinFor(ell);
+            const int tier = key->ksTier;
+            const uint32_t K = s->Kof(tier), beta = (ell + s->alpha - 1) / s->alpha;
+            const size_t stride = (size_t)(ell + K) * n;
+            auto& convs = SfheInternal::modupConv(this, ell, tier);
+            std::vector<std::vector<uint64_t>> ks(j - i);
+            BatchScope bs(this, (uint32_t)(j - i));  // (the batch ends with this block: the composed ops follow it)
+            for (; done < j; ++done) {
+                const MultSumOp& op = ops[done];
+                const auto& r = op.add.r;
+                if (r && r->c1 - r->c0 != (ptrdiff_t)s->polyWords(level + 1)) break;
+                std::vector<const uint64_t*> rows;
+                for (const MultTerm& t : op.terms)
+                    for (const uint64_t* p : {(const uint64_t*)t.first->c0, (const uint64_t*)t.first->c1,
+                                              (const uint64_t*)t.second->c0, (const uint64_t*)t.second->c1})
+                        rows.push_back(p);
+                const uint64_t* cst = nullptr;
+                if (op.add.c != 0.0) {
+                    ks[done - i] = SfheInternal::constResidues(s, op.add.c * s->scale[level + 1], ell - 1);
+                    cst = ks[done - i].data();
+                }
+                auto res = SfheInternal::newCt(this, level + 1, slots[done]);
+                auto acc = s->alloc(2 * stride);
+                auto ext = s->alloc(stride * beta);
+                auto scratch = s->alloc((size_t)2 * ell * n);
+                bs.lane((uint32_t)(done - i));
+                if (sfp_multn_relin_rescale_add(s->dev, res->c0, res->c1, rows.data(), (uint32_t)m, ell, K, s->Lq,
+                                                s->alpha, convs.data(), key->ptr, s->moddownConvOf(tier),
+                                                s->pInvModQof(tier), s->pModQof(tier), s->qInvTable[ell].data(),
+                                                acc->ptr, ext->ptr, scratch->ptr, r ? r->c0 : nullptr,
+                                                r ? r->c1 : nullptr, op.add.sign, cst) != 0)
+                    break;  // (declined: nothing issued for this op)
+                s->stats.sumn_fused++;
+                s->stats.keyswitch++;
+                s->stats.rescale++;
+                if (m > 1) s->stats.add++;
+                SfheInternal::countFused(s, op.add, ell - 1);
+                s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
+                s->countBytes(4.0 * ell * n * 8);
+                out[done] = SfheInternal::traced(this, res, "EvalMultSum");
+            }
+        }
+        // composed: the tensors, their components summed, one relinearisation + rescale, then the addend
+        for (size_t o = done; o < j; ++o) {
+            const MultSumOp& op = ops[o];
+            auto t = s->alloc(6 * pw);
+            uint64_t* d = t->ptr;
+            uint64_t* e = d + 3 * pw;
+            const sfp_limbs lm = s->qmap(ell);
+            for (size_t k = 0; k < m; ++k) {
+                const MultTerm& x = op.terms[k];
+                uint64_t* w = k ? e : d;
+                sfp_tensor(s->dev, w, w + pw, w + 2 * pw, x.first->c0, x.first->c1, x.second->c0, x.second->c1, lm);
+                if (k)
+                    for (int c = 0; c < 3; ++c) sfp_add(s->dev, d + c * pw, d + c * pw, e + c * pw, lm);
+            }
+            if (m > 1) s->stats.add++;
+            s->stats.sumn_composed++;
+            auto res = SfheInternal::relinRescale(this, d, d + pw, d + 2 * pw, level, slots[o]);
+            out[o] = SfheInternal::traced(this, addAfter(this, res, op.add), "EvalMultSum");
+        }
+        i = j;
+    }
+    return out;
+}
+
 Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMultAddPlain(
     const std::vector<Ciphertext<DCRTPoly>>& a, const std::vector<Plaintext>& p) {
     OpLock g(st.get());

@@ -454,6 +454,34 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     Ciphertext<DCRTPoly> EvalMultSum2(const Ciphertext<DCRTPoly>& a, const Ciphertext<DCRTPoly>& b,
                                       const Ciphertext<DCRTPoly>& a2, const Ciphertext<DCRTPoly>& b2,
                                       const Ciphertext<DCRTPoly>& r);
+    // Engine extension (the Chebyshev evaluator's remainder chains, DESIGN.md
+    // §4b): Rescale(Relin(sum_i a_i (x) b_i)) + addend for 1 <= m <=
+    // kMultSumMaxTerms terms, one level below the operands -- EvalMultSum2's
+    // contract with m pairs: every operand settled, all 2m at one level,
+    // a_i.scale * b_i.scale equal for all i; the addend's r null or canonical
+    // at the result's level (added, or subtracted with sign < 0), its constant
+    // c added at the result's scale.  A violation throws.  The composed form
+    // defines the integers: m sfp_tensor, their components summed (sfp_add),
+    // one relinearisation with its fused ModDown + rescale, then the addend.
+    // m = 2 gives EvalMultSum2's residues, m = 1 EvalMultAdd's.  Where the
+    // backend has prims.h sfp_multn_relin_rescale_add the sum is one
+    // product's launch chain; elsewhere (the C oracle, SFHE_MULT_SUM_FUSED=0
+    // -- read per call --, SFHE_FUSED_RESCALE=0, a level whose rows are dealt
+    // over ranks, the prim declining) the composed form runs: the same
+    // residues.  OpStats sumn_fused / sumn_composed count the ops of each kind.
+    static constexpr uint32_t kMultSumMaxTerms = 8;
+    using MultTerm = std::pair<Ciphertext<DCRTPoly>, Ciphertext<DCRTPoly>>;
+    struct MultSumOp {
+        std::vector<MultTerm> terms;
+        MultAddend add;
+    };
+    Ciphertext<DCRTPoly> EvalMultSum(const std::vector<MultTerm>& terms, const MultAddend& add);
+    // ... for independent ops: consecutive ops of one level AND one term count
+    // go out as one batch (EvalMultMany's path, runs of up to BatchWidth());
+    // ops of different term counts never share a batch
+    std::vector<Ciphertext<DCRTPoly>> EvalMultSumMany(const std::vector<MultSumOp>& ops);
+    // the condition of EvalMultSum that op violates (a message), or null
+    const char* MultSumViolation(const MultSumOp& op) const;
     // Engine extension: sum_i a_i * p_i with ONE rescale (same value and
     // level as summing the individually rescaled EvalMult(a_i, p_i)).
     Ciphertext<DCRTPoly> EvalMultAddPlain(const std::vector<Ciphertext<DCRTPoly>>& a,
@@ -753,6 +781,11 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         uint64_t select_columns = 0, fold_cols_fused = 0, fold_cols_composed = 0;
         uint64_t lex_fused = 0, lex_composed = 0;  // EvalLexStep tensors in one launch / composed of generic prims
         uint64_t dot_fused = 0, dot_composed = 0;  // EvalMultSum2 as one fused chain / composed of generic prims
+        uint64_t sumn_fused = 0, sumn_composed = 0;  // EvalMultSum(Many) ops likewise (EvalMultSum2's not included)
+        // EvalMultSumMany's runs of one level and term count (each goes out as one batch), and
+        // remainder chains of the Chebyshev evaluator that fell outside EvalMultSum's conditions
+        // and ran as separate products and sums
+        uint64_t sumn_batches = 0, sumn_fallbacks = 0;
     };
     OpStats GetOpStats() const;
     void ResetOpStats();
@@ -835,7 +868,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 13
+#define SFHE_FACADE_ABI_VERSION 14
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

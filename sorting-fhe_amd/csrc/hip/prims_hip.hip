@@ -586,6 +586,13 @@ __device__ __forceinline__ void nttRoundDyn(int b, u64* s, const NttTile& T, uin
 // [0, q)) forward values stay below 19q and inverse values below 2^9 q <
 // 2^51, so no intermediate reduction is needed.
 constexpr uint64_t kFpPrimeBound = 1ull << 42;
+// Products summed before one relinearisation (sfp_multn_relin_rescale_add):
+// the fold and the tensor epilogue reduce the exact sum of all once.  FP64
+// rows: 2 m terms below 2q each stay under fpMulMod's 2^52; integer rows: 2 m
+// products of operands below 2^60 stay inside 128 bits.
+constexpr int kMultSumMax = SFP_MULT_SUM_MAX;
+static_assert(4ull * kMultSumMax * kFpPrimeBound < (1ull << 52), "the FP64 fold's sum of 2m terms exceeds 2^52");
+static_assert(2ull * kMultSumMax <= (1ull << 8), "2m products below 2^120 exceed 128 bits");
 
 __device__ __forceinline__ double fpMulMod(double y, double w, double wq, double q) {
     const double hi = y * w;
@@ -833,10 +840,12 @@ struct RowGroup {
     // of polynomial p, coefficient form; pre = its dropped row l (with rescale)
     const struct MdColArgs* md;
     uint32_t esumNeg;
-    // a second product summed with the first (sfp_mult2_relin_rescale_add): a
-    // device array of its four row bases (a0', a1', b0', b1'; row i at + i n).
-    // Inverse first pass with `pre`: the rows are src * pre + a1' * b1'; forward
-    // epilogue with tA0: the tensor gains the second quadruple's products.
+    // further products summed with the first (sfp_multn_relin_rescale_add):
+    // t2n of them, t2 a device array of their row bases, four each (a0', a1',
+    // b0', b1' of set j at t2[4 j ..]; row i at + i n).  Inverse first pass with
+    // `pre`: the rows are src * pre + sum_j a1' * b1'; forward epilogue with
+    // tA0: the tensor gains every further quadruple's products.
+    uint32_t t2n;
     const u64* const* t2;
 };
 
@@ -898,7 +907,7 @@ __device__ unsigned long long g_mdrsTrace[kTraceSlots][8];  // k_mdrsf (FP64 blo
 #define NTT_MARK(i)
 #endif
 
-// DOT: the two-product forms (RowGroup::t2) are compiled in; the launch sites
+// DOT: the several-product forms (RowGroup::t2) are compiled in; the launch sites
 // pick these instantiations only for a group that carries t2, so every other
 // launch runs the kernel exactly as it compiles without them (their loads
 // cost the single-product forms up to three waves per SIMD).
@@ -1035,7 +1044,7 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
 #pragma unroll
         for (int k = 0; k < NPAIR; ++k) mr[k] = *reinterpret_cast<const ulonglong2*>(pre + tileOff(k));
     }
-    // (the inverse ROW pass alone: a sum of two products' d2 enters through ModUp's INTT)
+    // (the inverse ROW pass alone: a sum of several products' d2 enters through ModUp's INTT)
     constexpr bool kPre2 = DOT && INV && !COL;
     ulonglong2 xr2[kPre2 ? NPAIR : 1], mr2[kPre2 ? NPAIR : 1];
     bool pre2 = false;
@@ -1126,6 +1135,14 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
                     if (pre2) {
                         x.x = sf_add(x.x, bmul(xr2[k].x, mr2[k].x, LB), q);
                         x.y = sf_add(x.y, bmul(xr2[k].y, mr2[k].y, LB), q);
+                        // (a third product and on: read here, not held with the tile)
+                        for (uint32_t j = 1; j < G.t2n; ++j) {
+                            const size_t ro = ((size_t)ii << logn) + g;
+                            const ulonglong2 x3 = *reinterpret_cast<const ulonglong2*>(G.t2[4 * j + 1] + ro);
+                            const ulonglong2 m3 = *reinterpret_cast<const ulonglong2*>(G.t2[4 * j + 3] + ro);
+                            x.x = sf_add(x.x, bmul(x3.x, m3.x, LB), q);
+                            x.y = sf_add(x.y, bmul(x3.y, m3.y, LB), q);
+                        }
                     }
                 }
             }
@@ -1208,16 +1225,13 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
     // (forward passes only: the inverse COL pass keeps its post factors in these fields)
     const u64* esm = !INV && epi && G.esum.base ? rowAt(G.esum, pp, ii) : nullptr;
     const u64 ecs = !INV && epi && G.ecst ? G.ecst[pp * G.R + ii] : 0;
-    // (the forward ROW pass alone: the second product's rows, sfp_mult2_relin_rescale_add)
+    // (the forward ROW pass alone: the further products' rows, sfp_multn_relin_rescale_add)
     constexpr bool kTens2 = DOT && !INV && !COL;
-    const u64 *uA0 = nullptr, *uA1 = nullptr, *uB0 = nullptr, *uB1 = nullptr;
+    // (every further set in one run-time loop: with the first set read straight-line
+    // and the loop from the second, the pass needs 94-95 VGPRs instead of 86)
+    uint32_t nT2 = 0;
     if constexpr (kTens2) {
-        if (tens && G.t2) {
-            uA0 = G.t2[0];
-            uA1 = G.t2[1];
-            uB0 = G.t2[2];
-            uB1 = G.t2[3];
-        }
+        if (tens && G.t2) nT2 = G.t2n;
     }
 #pragma unroll
     for (int k = 0; k < NPAIR; ++k) {
@@ -1275,28 +1289,35 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt(const RowGroupSet<NG> GS, co
                 if (tens) {  // the tensor product's polynomial pp at (row ii, g)
                     const ulonglong2 a0 = *reinterpret_cast<const ulonglong2*>(G.tA0 + trow + g);
                     const ulonglong2 b0 = *reinterpret_cast<const ulonglong2*>(G.tB0 + trow + g);
-                    if (kTens2 && uA0) {  // both quadruples' products, one reduction of their exact sum
-                        const ulonglong2 c0 = *reinterpret_cast<const ulonglong2*>(uA0 + trow + g);
-                        const ulonglong2 e0 = *reinterpret_cast<const ulonglong2*>(uB0 + trow + g);
+                    if (kTens2 && nT2) {  // every quadruple's products, one reduction of their exact sum
+                        // (at most 2 kMultSumMax products below 2^120 each: inside 128 bits)
                         Acc t{0, 0}, u{0, 0};
                         if (pp == 0) {
                             macc(t, a0.x, b0.x);
-                            macc(t, c0.x, e0.x);
                             macc(u, a0.y, b0.y);
-                            macc(u, c0.y, e0.y);
+                            for (uint32_t j = 0; j < nT2; ++j) {
+                                const ulonglong2 f0 = *reinterpret_cast<const ulonglong2*>(G.t2[4 * j] + trow + g);
+                                const ulonglong2 h0 = *reinterpret_cast<const ulonglong2*>(G.t2[4 * j + 2] + trow + g);
+                                macc(t, f0.x, h0.x);
+                                macc(u, f0.y, h0.y);
+                            }
                         } else {
                             const ulonglong2 a1 = *reinterpret_cast<const ulonglong2*>(G.tA1 + trow + g);
                             const ulonglong2 b1 = *reinterpret_cast<const ulonglong2*>(G.tB1 + trow + g);
-                            const ulonglong2 c1 = *reinterpret_cast<const ulonglong2*>(uA1 + trow + g);
-                            const ulonglong2 e1 = *reinterpret_cast<const ulonglong2*>(uB1 + trow + g);
                             macc(t, a0.x, b1.x);
                             macc(t, a1.x, b0.x);
-                            macc(t, c0.x, e1.x);
-                            macc(t, c1.x, e0.x);
                             macc(u, a0.y, b1.y);
                             macc(u, a1.y, b0.y);
-                            macc(u, c0.y, e1.y);
-                            macc(u, c1.y, e0.y);
+                            for (uint32_t j = 0; j < nT2; ++j) {
+                                const ulonglong2 f0 = *reinterpret_cast<const ulonglong2*>(G.t2[4 * j] + trow + g);
+                                const ulonglong2 f1 = *reinterpret_cast<const ulonglong2*>(G.t2[4 * j + 1] + trow + g);
+                                const ulonglong2 h0 = *reinterpret_cast<const ulonglong2*>(G.t2[4 * j + 2] + trow + g);
+                                const ulonglong2 h1 = *reinterpret_cast<const ulonglong2*>(G.t2[4 * j + 3] + trow + g);
+                                macc(t, f0.x, h1.x);
+                                macc(t, f1.x, h0.x);
+                                macc(u, f0.y, h1.y);
+                                macc(u, f1.y, h0.y);
+                            }
                         }
                         o.x = sf_reduce128_acc(t.lo, t.hi, &EB);
                         o.y = sf_reduce128_acc(u.lo, u.hi, &EB);
@@ -1669,10 +1690,12 @@ struct KsArgs {
     // non-null: the fold rows are the tensor's d0 = a0 b0, d1 = a0 b1 + a1 b0
     // at row ell - 1, formed here (fold0 / fold1 unused)
     const u64 *fa0, *fa1, *fb0, *fb1;
-    // non-null (with fa0 and inMul): a second product summed with the first
-    // (sfp_mult2_relin_rescale_add) -- the own limbs are in (.) inMul + ga1 (.) gb1
-    // and the fold rows gain the second tensor's d0 / d1
-    const u64 *ga0, *ga1, *gb0, *gb1;
+    // non-null (with fa0 and inMul): gn further products summed with the first
+    // (sfp_multn_relin_rescale_add), g2 a device array of their row bases, four
+    // each (RowGroup::t2's array) -- the own limbs are in (.) inMul + sum_j a1' (.) b1'
+    // and the fold rows gain every further tensor's d0 / d1
+    const u64* const* g2;
+    uint32_t gn;
     uint32_t ell, Lq, alpha, beta;
     int accum;  // acc += the inner product
     // rows t >= invFrom (the P limbs, and for a ModDown fused with its rescale
@@ -1683,7 +1706,7 @@ struct KsArgs {
     const double* itwD;
 };
 
-// DOT: with the second product's rows (KsArgs::ga0 ..) compiled in, as k_ntt's
+// DOT: with the further products' rows (KsArgs::g2) compiled in, as k_ntt's
 template <int LE, int TILE, int NG = 1, bool DOT = false>
 __global__ __launch_bounds__(TILE >> LE) void k_ntt_ks(const ArgSet<KsArgs, NG> AS, const sf_barrett* __restrict__ bar,
                                                      const u64* __restrict__ tw, const u64* __restrict__ twS,
@@ -1799,12 +1822,14 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt_ks(const ArgSet<KsArgs, NG> 
                         const ulonglong2 m = *reinterpret_cast<const ulonglong2*>(mul + e);
                         x.x = bmul(x.x, m.x, B);
                         x.y = bmul(x.y, m.y, B);
-                        if (DOT && A.ga1) {
+                        if (DOT && A.g2) {
                             const size_t ro = (size_t)t * n + rowOff + e;
-                            const ulonglong2 x2 = *reinterpret_cast<const ulonglong2*>(A.ga1 + ro);
-                            const ulonglong2 m2 = *reinterpret_cast<const ulonglong2*>(A.gb1 + ro);
-                            x.x = sf_add(x.x, bmul(x2.x, m2.x, B), q);
-                            x.y = sf_add(x.y, bmul(x2.y, m2.y, B), q);
+                            for (uint32_t u = 0; u < A.gn; ++u) {
+                                const ulonglong2 x2 = *reinterpret_cast<const ulonglong2*>(A.g2[4 * u + 1] + ro);
+                                const ulonglong2 m2 = *reinterpret_cast<const ulonglong2*>(A.g2[4 * u + 3] + ro);
+                                x.x = sf_add(x.x, bmul(x2.x, m2.x, B), q);
+                                x.y = sf_add(x.y, bmul(x2.y, m2.y, B), q);
+                            }
                         }
                     }
                     if constexpr (FP) {
@@ -1928,11 +1953,12 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt_ks(const ArgSet<KsArgs, NG> 
                         double f0x = fpMulMod(qx0, b0x, b0x * qi, qd), f0y = fpMulMod(qy0, b0y, b0y * qi, qd);
                         double f1x = fpMulMod(qx0, b1x, b1x * qi, qd) + fpMulMod(qx1, b0x, b0x * qi, qd);
                         double f1y = fpMulMod(qy0, b1y, b1y * qi, qd) + fpMulMod(qy1, b0y, b0y * qi, qd);
-                        if (DOT && A.ga0) {  // (each term |r| < 2q: the sums stay far below fpMulMod's 2^52)
-                            const ulonglong2 z0 = *reinterpret_cast<const ulonglong2*>(A.ga0 + ro);
-                            const ulonglong2 z1 = *reinterpret_cast<const ulonglong2*>(A.ga1 + ro);
-                            const ulonglong2 w0 = *reinterpret_cast<const ulonglong2*>(A.gb0 + ro);
-                            const ulonglong2 w1 = *reinterpret_cast<const ulonglong2*>(A.gb1 + ro);
+                        // (each term |r| < 2q, 2 kMultSumMax of them: below fpMulMod's 2^52, kMultSumMax's static_assert)
+                        for (uint32_t u = 0; DOT && A.g2 && u < A.gn; ++u) {
+                            const ulonglong2 z0 = *reinterpret_cast<const ulonglong2*>(A.g2[4 * u] + ro);
+                            const ulonglong2 z1 = *reinterpret_cast<const ulonglong2*>(A.g2[4 * u + 1] + ro);
+                            const ulonglong2 w0 = *reinterpret_cast<const ulonglong2*>(A.g2[4 * u + 2] + ro);
+                            const ulonglong2 w1 = *reinterpret_cast<const ulonglong2*>(A.g2[4 * u + 3] + ro);
                             const double cx0 = u2d(z0.x), cy0 = u2d(z0.y), cx1 = u2d(z1.x), cy1 = u2d(z1.y);
                             const double e0x = u2d(w0.x), e0y = u2d(w0.y), e1x = u2d(w1.x), e1y = u2d(w1.y);
                             f0x += fpMulMod(cx0, e0x, e0x * qi, qd);
@@ -1951,11 +1977,11 @@ __global__ __launch_bounds__(TILE >> LE) void k_ntt_ks(const ArgSet<KsArgs, NG> 
                         macc(uu, x0.y, y1.y);
                         macc(uu, x1.y, y0.y);
                         u64 g0x = bmul(x0.x, y0.x, B), g0y = bmul(x0.y, y0.y, B);
-                        if (DOT && A.ga0) {
-                            const ulonglong2 z0 = *reinterpret_cast<const ulonglong2*>(A.ga0 + ro);
-                            const ulonglong2 z1 = *reinterpret_cast<const ulonglong2*>(A.ga1 + ro);
-                            const ulonglong2 w0 = *reinterpret_cast<const ulonglong2*>(A.gb0 + ro);
-                            const ulonglong2 w1 = *reinterpret_cast<const ulonglong2*>(A.gb1 + ro);
+                        for (uint32_t u = 0; DOT && A.g2 && u < A.gn; ++u) {
+                            const ulonglong2 z0 = *reinterpret_cast<const ulonglong2*>(A.g2[4 * u] + ro);
+                            const ulonglong2 z1 = *reinterpret_cast<const ulonglong2*>(A.g2[4 * u + 1] + ro);
+                            const ulonglong2 w0 = *reinterpret_cast<const ulonglong2*>(A.g2[4 * u + 2] + ro);
+                            const ulonglong2 w1 = *reinterpret_cast<const ulonglong2*>(A.g2[4 * u + 3] + ro);
                             macc(tt, z0.x, w1.x);
                             macc(tt, z1.x, w0.x);
                             macc(uu, z0.y, w1.y);
@@ -4379,12 +4405,14 @@ static auto withWidth(int cnt, F&& f) {
 // -- "Cannot find Symbol" at launch.)
 using NttKerns = SetKerns<RowGroup, const sf_barrett*, const u64*, const u64*, const u64*, const u64*, uint32_t,
                           const double*, const double*, const double*, const double*, int, const double*>;
-// (DOT, the two-product forms: one set or a merged pair -- the sort's two lanes)
+// (DOT, the several-product forms: one set, a merged pair -- the sort's two
+// lanes -- and four, which a wave of the Chebyshev evaluator's remainder
+// chains reaches; the metric sort never merges eight of them)
 template <bool INV, bool COL, int LE, int TILE, bool CONV = false, bool DOT = false>
 static NttKerns nttKerns() {
     if constexpr (DOT && LE == 2)
-        return {k_ntt<INV, COL, LE, TILE, 1, CONV, true>, k_ntt<INV, COL, LE, TILE, 2, CONV, true>, nullptr, nullptr,
-                TILE, TILE >> LE};
+        return {k_ntt<INV, COL, LE, TILE, 1, CONV, true>, k_ntt<INV, COL, LE, TILE, 2, CONV, true>,
+                k_ntt<INV, COL, LE, TILE, 4, CONV, true>, nullptr, TILE, TILE >> LE};
     else if constexpr (DOT)
         return {k_ntt<INV, COL, LE, TILE, 1, CONV, true>, nullptr, nullptr, nullptr, TILE, TILE >> LE};
     else if constexpr (LE == 2)
@@ -4408,7 +4436,8 @@ using KsKerns = SetKerns<KsArgs, const sf_barrett*, const u64*, const u64*, uint
 template <int TILE, bool DOT = false>
 static KsKerns ksKerns() {
     if constexpr (DOT)
-        return {k_ntt_ks<2, TILE, 1, true>, k_ntt_ks<2, TILE, 2, true>, nullptr, nullptr, TILE, TILE >> 2};
+        return {k_ntt_ks<2, TILE, 1, true>, k_ntt_ks<2, TILE, 2, true>, k_ntt_ks<2, TILE, 4, true>, nullptr, TILE,
+                TILE >> 2};
     else
         return {k_ntt_ks<2, TILE, 1>, k_ntt_ks<2, TILE, 2>, k_ntt_ks<2, TILE, 4>, k_ntt_ks<2, TILE, 8>, TILE,
                 TILE >> 2};
@@ -6707,14 +6736,13 @@ static bool ksFuse() {  // SFHE_KS_FUSE=0: the unfused sequences (A/B)
 // INTT of the input (in, or in (.) inMul: a tensor's d2 = a1 b1 formed in the
 // first pass), the digits' conversions, the forward COL pass, then k_ntt_ks.
 // T[4] (a0, a1, b0, b1) non-null: the fold rows are the tensor's d0 / d1.
-// T2[4] (with T and inMul): a second product's rows, summed with the first's
-// wherever those are read (t2dev: their device copy for k_ntt).
+// t2dev (with T and inMul): t2n further products' row bases (a device array,
+// four per product), summed with the first's wherever those are read.
 static void modupInnerCore(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uint64_t* in, const uint64_t* inMul,
                            uint32_t ell, uint32_t K, uint32_t Lq, uint32_t alpha, const sfp_conv* const* convs,
                            const uint64_t* key, const uint64_t* fold0, const uint64_t* fold1,
                            const uint64_t* const* T, uint64_t foldK, int accum, uint32_t invFrom, uint64_t* ext,
-                           uint64_t* scr, int phases = 3, const uint64_t* const* T2 = nullptr,
-                           const u64* const* t2dev = nullptr) {
+                           uint64_t* scr, int phases = 3, const u64* const* t2dev = nullptr, uint32_t t2n = 0) {
     const uint32_t n = d->n;
     const uint32_t beta = (ell + alpha - 1) / alpha;
     const long long stride = (long long)(ell + K) * n;
@@ -6724,7 +6752,10 @@ static void modupInnerCore(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uin
     A.src = RowPtr{in, 0, (long long)n};
     A.dst = RowPtr{scr, 0, (long long)n};
     if (inMul) A.pre = RowPtr{inMul, 0, (long long)n};
-    if (inMul && T2) A.t2 = t2dev;
+    if (inMul && t2dev) {
+        A.t2 = t2dev;
+        A.t2n = t2n;
+    }
     RowGroup B = rowsOf(beta, ell + K, sfp_limbs{ell + K, ell, Lq, 0});
     B.src = B.dst = RowPtr{ext, stride, (long long)n};
     B.skipEll = ell;
@@ -6764,11 +6795,9 @@ static void modupInnerCore(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uin
         a.fa1 = T[1];
         a.fb0 = T[2];
         a.fb1 = T[3];
-        if (T2 && inMul) {
-            a.ga0 = T2[0];
-            a.ga1 = T2[1];
-            a.gb0 = T2[2];
-            a.gb1 = T2[3];
+        if (t2dev && inMul) {
+            a.g2 = t2dev;
+            a.gn = t2n;
         }
     }
     a.foldK = foldK;
@@ -6785,7 +6814,7 @@ static void modupInnerCore(sfp_dev* d, uint64_t* acc0, uint64_t* acc1, const uin
     const size_t total = (size_t)rows * n;
     const KsArgs* pa = &a;
     const bool small = nttSmallTile(d, rows, kKsT1kRows);
-    const KsKerns kerns = a.ga0 ? (small ? ksKerns<kNttSmallTile, true>() : ksKerns<kNttTile, true>())
+    const KsKerns kerns = a.g2 ? (small ? ksKerns<kNttSmallTile, true>() : ksKerns<kNttTile, true>())
                                 : (small ? ksKerns<kNttSmallTile>() : ksKerns<kNttTile>());
     timedLaunch(d, SFP_FAM_NTTKS, 8.0 * total * (3.0 * beta + (accum ? 4.0 : 2.0)),
                 [&] { issueSets(d, STK_KS, kerns, &pa, &rows, 1, nttTables(d, 0)); });
@@ -7151,7 +7180,7 @@ static void moddownRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, const
                                const uint64_t* const* T, uint64_t* acc, size_t accStride, uint32_t ell, uint32_t K,
                                uint32_t Lq, const sfp_conv* c, const uint64_t* pinv, const uint64_t* pmod,
                                const uint64_t* qlinv, uint64_t* scr, int rowDone, const EpiAdd& ea = EpiAdd{},
-                               const u64* const* t2dev = nullptr) {
+                               const u64* const* t2dev = nullptr, uint32_t t2n = 0) {
     const uint32_t n = d->n, l = ell - 1;
     if (ell < 2 || ell > SFP_MAX_LIMBS || !c || c->ns > (uint32_t)kMaxConvSrc || c->nt < ell ||
         !limbsOk(d, sfp_limbs{K + 1, 1, Lq, l}, "moddown_rescale")) {
@@ -7273,7 +7302,8 @@ static void moddownRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, const
         B.tA1 = T[1];
         B.tB0 = T[2];
         B.tB1 = T[3];
-        B.t2 = t2dev;  // (a second product's rows: the tensor is the sum of both)
+        B.t2 = t2dev;  // (further products' rows: the tensor is the sum of all)
+        B.t2n = t2dev ? t2n : 0;
     } else {
         B.eadd = RowPtr{d0, (long long)(d1 - d0), (long long)n};
     }
@@ -7297,7 +7327,8 @@ static int multRelinRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, cons
                                 const uint64_t* b0, const uint64_t* b1, uint32_t ell, uint32_t K, uint32_t Lq,
                                 uint32_t alpha, const sfp_conv* const* convs, const uint64_t* key, const sfp_conv* c,
                                 const uint64_t* pinv, const uint64_t* pmod, const uint64_t* qlinv, uint64_t* acc,
-                                uint64_t* ext, uint64_t* scr, const EpiAdd& ea, const uint64_t* const* T2 = nullptr) {
+                                uint64_t* ext, uint64_t* scr, const EpiAdd& ea, const uint64_t* const* T2 = nullptr,
+                                uint32_t t2n = 0) {
     const uint32_t beta = (ell + alpha - 1) / alpha;
     if (!ksFuse() || d->n <= (uint32_t)kNttTile) return -1;
     if (ell < 2 || beta > (uint32_t)kMaxConvJobs || ell + K > SFP_MAX_LIMBS) {
@@ -7305,20 +7336,21 @@ static int multRelinRescaleCore(sfp_dev* d, uint64_t* out0, uint64_t* out1, cons
         return 0;
     }
     const uint64_t* T[4] = {a0, a1, b0, b1};
-    // the second product's row bases, where k_ntt's argument block has one pointer for them
+    // the further products' row bases (T2: four per product, t2n products),
+    // where the kernels' argument blocks have one pointer for them
     const u64* const* t2dev = nullptr;
     if (T2) {
-        u64 w[4];
-        for (int i = 0; i < 4; ++i) w[i] = (u64)(uintptr_t)T2[i];
-        t2dev = reinterpret_cast<const u64* const*>(devConst(d, w, 4));
+        u64 w[4 * (kMultSumMax - 1)];
+        for (uint32_t i = 0; i < 4 * t2n; ++i) w[i] = (u64)(uintptr_t)T2[i];
+        t2dev = reinterpret_cast<const u64* const*>(devConst(d, w, 4 * t2n));
         if (!t2dev) return 0;  // (recorded)
     }
     // d2 = a1 b1 in the ModUp's first pass and the own digits; d0, d1 at row
     // ell - 1 in the inner product's fold, the rest in the ModDown's epilogue
     modupInnerCore(d, acc, acc + (size_t)(ell + K) * d->n, a1, b1, ell, K, Lq, alpha, convs, key, nullptr, nullptr,
-                   T, pmod[ell - 1], 0, ell - 1, ext, scr, 3, T2, t2dev);
+                   T, pmod[ell - 1], 0, ell - 1, ext, scr, 3, t2dev, t2n);
     moddownRescaleCore(d, out0, out1, nullptr, nullptr, T, acc, (size_t)(ell + K) * d->n, ell, K, Lq, c, pinv, pmod,
-                       qlinv, scr, 1, ea, t2dev);
+                       qlinv, scr, 1, ea, t2dev, t2n);
     return 0;
 }
 
@@ -7368,7 +7400,29 @@ int sfp_mult2_relin_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, cons
     if (!a0 || !a1 || !b0 || !b1 || !c0 || !c1 || !e0 || !e1 || (bits & 15)) return -1;
     const uint64_t* T2[4] = {c0, c1, e0, e1};
     return multRelinRescaleCore(d, out0, out1, a0, a1, b0, b1, ell, K, Lq, alpha, convs, key, c, pinv, pmod, qlinv,
-                                acc, ext, scr, EpiAdd{r0, r1, sign, cstBoth(cst, ell - 1, kb)}, T2);
+                                acc, ext, scr, EpiAdd{r0, r1, sign, cstBoth(cst, ell - 1, kb)}, T2, 1);
+}
+
+int sfp_multn_relin_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* const* rows, uint32_t m,
+                                uint32_t ell, uint32_t K, uint32_t Lq, uint32_t alpha, const sfp_conv* const* convs,
+                                const uint64_t* key, const sfp_conv* c, const uint64_t* pinv, const uint64_t* pmod,
+                                const uint64_t* qlinv, uint64_t* acc, uint64_t* ext, uint64_t* scr, const uint64_t* r0,
+                                const uint64_t* r1, int sign, const uint64_t* cst) {
+    uint64_t kb[2 * SFP_MAX_LIMBS];
+    // declined (nothing done): no or too many products, a missing row set, rows
+    // the 16-byte accesses cannot take, a one-tile ring (the small-ring kernel
+    // has no several-product form)
+    if (ell < 2 || ell > SFP_MAX_LIMBS || !rows || m < 1 || m > (uint32_t)kMultSumMax) return -1;
+    if (!ksFuse() || d->n <= (uint32_t)kNttTile) return -1;
+    uintptr_t bits = 0;
+    for (uint32_t i = 0; i < 4 * m; ++i) {
+        if (!rows[i]) return -1;
+        bits |= (uintptr_t)rows[i];
+    }
+    if (bits & 15) return -1;
+    return multRelinRescaleCore(d, out0, out1, rows[0], rows[1], rows[2], rows[3], ell, K, Lq, alpha, convs, key, c,
+                                pinv, pmod, qlinv, acc, ext, scr, EpiAdd{r0, r1, sign, cstBoth(cst, ell - 1, kb)},
+                                m > 1 ? rows + 4 : nullptr, m - 1);
 }
 
 int sfp_moddown_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1, const uint64_t* d0, const uint64_t* d1,

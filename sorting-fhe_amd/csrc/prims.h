@@ -360,6 +360,26 @@ SFP_OPTIONAL int sfp_mult2_relin_rescale_add(sfp_dev* d, uint64_t* out0, uint64_
                                              uint64_t* acc, uint64_t* ext, uint64_t* scratch, const uint64_t* r0,
                                              const uint64_t* r1, int sign, const uint64_t* cst);
 
+// ---- optional: the sum of m products relinearised once ---------------------------
+// out = Rescale(Relin(sum_i a_i (x) b_i)) (+- r, + cst), 1 <= m <= SFP_MULT_SUM_MAX:
+// sfp_mult2_relin_rescale_add's integers with m quadruples -- each component
+// the canonical residue of the sum of the m tensors' canonical components
+// (sfp_tensor m times, sfp_add per component), then sfp_modup +
+// sfp_ks_inner_fold + sfp_moddown_rescale and the sum.  One product's launch
+// chain: its three operand-reading passes loop over the further row sets.
+// rows: 4 m host pointers, (a0, a1, b0, b1) of product i at rows[4 i ..]; the
+// other arguments as sfp_mult_relin_rescale_add.  m = 1 is that prim, m = 2
+// is sfp_mult2_relin_rescale_add.  Returns -1 (declined, nothing done) for m
+// out of range, a null or misaligned row set, or a ring of one NTT tile.
+#define SFP_MULT_SUM_MAX 8
+SFP_OPTIONAL int sfp_multn_relin_rescale_add(sfp_dev* d, uint64_t* out0, uint64_t* out1,
+                                             const uint64_t* const* rows, uint32_t m, uint32_t ell, uint32_t K,
+                                             uint32_t Lq, uint32_t alpha, const sfp_conv* const* convs,
+                                             const uint64_t* key, const sfp_conv* c, const uint64_t* pinv,
+                                             const uint64_t* pmod, const uint64_t* qlinv, uint64_t* acc, uint64_t* ext,
+                                             uint64_t* scratch, const uint64_t* r0, const uint64_t* r1, int sign,
+                                             const uint64_t* cst);
+
 // ---- optional: several constant rescales of one input in one launch pair per direction
 // Term j of m (2 <= m <= SFP_MAX_CONST_TERMS) is sfp_mul_const_rescale(_add)
 // of the input's first ell_j rows: out_j = Rescale(in * k_j) (+ cst_j), k_j

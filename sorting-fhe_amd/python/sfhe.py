@@ -57,6 +57,8 @@ ABI_SYMBOLS = [
     "sfhe_lex_sort_depth", "sfhe_sorter_rank_lex", "sfhe_sorter_sort_records_lex", "sfhe_sorter_select_records_lex",
     "sfhe_eval_lex_step", "sfhe_lex_counts",
     "sfhe_eval_mult_sum2", "sfhe_dot_counts",
+    "sfhe_eval_mult_sum", "sfhe_sumn_counts",
+    "sfhe_eval_mult_sum_many", "sfhe_sumn_batch_counts", "sfhe_ct_relabel_scale",
 ]
 
 MAX_COLUMNS = 8  # SFHE_MAX_COLUMNS
@@ -212,6 +214,11 @@ _SIGS = {
     "sfhe_lex_counts": (C.c_int, [_VP, _PU64, _PU64]),
     "sfhe_eval_mult_sum2": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _PVP]),
     "sfhe_dot_counts": (C.c_int, [_VP, _PU64, _PU64]),
+    "sfhe_eval_mult_sum": (C.c_int, [_VP, _PVP, _PVP, C.c_size_t, _VP, _PVP]),
+    "sfhe_sumn_counts": (C.c_int, [_VP, _PU64, _PU64]),
+    "sfhe_eval_mult_sum_many": (C.c_int, [_VP, _PVP, _PVP, C.POINTER(C.c_size_t), C.c_size_t, _PVP, _PVP]),
+    "sfhe_sumn_batch_counts": (C.c_int, [_VP, _PU64, _PU64]),
+    "sfhe_ct_relabel_scale": (C.c_int, [_VP, C.c_double, _PVP]),
 }
 
 _libs: dict = {}
@@ -535,6 +542,44 @@ class Engine:
         """a*b + a2*b2 (+ r), one level below the operands, from ONE relinearisation and
         rescale (operands at one level; r, if given, at the result's level)."""
         return self._new(self.lib.sfhe_eval_mult_sum2, self.ctx, a.h, b.h, a2.h, b2.h, r.h if r is not None else None)
+
+    def mult_sum(self, terms, r=None):
+        """sum of a*b over the (a, b) pairs of terms (+ r), one level below the operands, from ONE
+        relinearisation and rescale (all operands at one level; r, if given, at the result's level)."""
+        n = len(terms)
+        a = (C.c_void_p * n)(*[t[0].h for t in terms])
+        b = (C.c_void_p * n)(*[t[1].h for t in terms])
+        return self._new(self.lib.sfhe_eval_mult_sum, self.ctx, a, b, n, r.h if r is not None else None)
+
+    def mult_sum_many(self, ops):
+        """[mult_sum(terms, r) for terms, r in ops] in one call: consecutive ops of one level and one
+        term count go out as one batch; each result equals the op issued alone."""
+        flat = [t for terms, _ in ops for t in terms]
+        n = len(flat)
+        a = (C.c_void_p * n)(*[t[0].h for t in flat])
+        b = (C.c_void_p * n)(*[t[1].h for t in flat])
+        counts = (C.c_size_t * len(ops))(*[len(terms) for terms, _ in ops])
+        r = (C.c_void_p * len(ops))(*[x.h if x is not None else None for _, x in ops])
+        out = (C.c_void_p * len(ops))()
+        self._chk(self.lib.sfhe_eval_mult_sum_many(self.ctx, a, b, counts, len(ops), r, out))
+        return [Ct(self, C.c_void_p(h)) for h in out]
+
+    def sumn_batch_counts(self):
+        """(batches, fallbacks): runs of one level and term count that mult_sum / mult_sum_many (the
+        Chebyshev evaluator's included) issued, and evaluator chains that ran as separate products."""
+        f, c = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_sumn_batch_counts(self.ctx, C.byref(f), C.byref(c)))
+        return f.value, c.value
+
+    def relabel_scale(self, ct, factor):
+        """A copy of ct with its scale label multiplied by factor (rows untouched; for tests)."""
+        return self._new(self.lib.sfhe_ct_relabel_scale, ct.h, float(factor))
+
+    def sumn_counts(self):
+        """(fused, composed) mult_sum ops (the Chebyshev evaluator's included) since the last op_stats reset."""
+        f, c = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_sumn_counts(self.ctx, C.byref(f), C.byref(c)))
+        return f.value, c.value
 
     def dot_counts(self):
         """(fused, composed) mult_sum2 calls (the sign polynomials' included) since the last op_stats reset."""
