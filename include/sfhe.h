@@ -41,7 +41,9 @@ extern "C" {
  * sfhe_eval_lex_step, sfhe_lex_counts, and the sum of two products:
  * sfhe_eval_mult_sum2, sfhe_dot_counts, and the sum of n products:
  * sfhe_eval_mult_sum, sfhe_eval_mult_sum_many, sfhe_sumn_counts,
- * sfhe_sumn_batch_counts, sfhe_ct_relabel_scale) */
+ * sfhe_sumn_batch_counts, sfhe_ct_relabel_scale, and the grouping by a key:
+ * sfhe_group_params, sfhe_sorter_group, sfhe_eval_gate_sum_many,
+ * sfhe_group_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -435,6 +437,42 @@ int sfhe_sumn_batch_counts(sfhe_ctx* c, uint64_t* batches, uint64_t* fallbacks);
 /* A copy of ct whose scale label is multiplied by factor (the rows are not
  * touched): for testing how the evaluator treats operands of unequal scales. */
 int sfhe_ct_relabel_scale(const sfhe_ct* ct, double factor, sfhe_ct** out);
+/* Engine extensions (additions at ABI 3): grouping rows by an encrypted key --
+ * COUNT(*), SUM(col) and ROW_NUMBER() OVER (PARTITION BY key), every result in
+ * the rows' input order.  `keys` and the 0 <= ncols <= SFHE_MAX_COLUMNS payload
+ * columns sit at one level and slot count.  *count: slot r holds the number of
+ * rows whose key equals row r's (row r included).  *index (want_index != 0;
+ * else set to NULL and `index` may be NULL): slot r holds the number of rows
+ * before r with r's key, so the first row of every group holds 0.  sums_out[c]:
+ * slot r holds the sum of column c over the rows with r's key.  *count is one
+ * level above the others, which end at the context's sfhe_group_params depth.
+ * Two keys must be equal or at least the sign configuration's resolution apart
+ * (1/N for the defaults).  No placement is evaluated: the depth is the stable
+ * rank's.
+ * sfhe_group_params: the mult_depth of sfhe_sorter_group with N's default sign
+ * configuration, and the rotation amounts it uses (the rank's: baby steps,
+ * giant steps, batch offsets and partition folds in the layout of ring 2^17; at
+ * a smaller ring the entry uses a subset of them or composes its own from
+ * them).  cap / count as sfhe_direct_sort_params.
+ * A column count out of range, a NULL entry or columns at another level or slot
+ * count than the key: SFHE_EINVAL; too little depth: SFHE_ESCHEME, the message
+ * naming the depth needed, before anything is computed.  Always eager. */
+int sfhe_group_params(uint32_t N, uint32_t* mult_depth, int32_t* rotations, size_t cap, size_t* count);
+int sfhe_sorter_group(sfhe_sorter* s, const sfhe_ct* keys, const sfhe_ct* const* cols, size_t ncols, int want_index,
+                      int n, int dg, int df, sfhe_ct** count, sfhe_ct** index, sfhe_ct** sums_out);
+/* outs[c] = sum_b (1 - q[b]) (.) u[c * nq + b], relinearised once per column,
+ * one level below q: the grouping's gated column sums.  The nq >= 1 gates sit
+ * at one level and scale; an operand may have more limbs than the gates (a
+ * numerically lower level), a column's operands share one scale; 0 <= ncols <=
+ * SFHE_MAX_COLUMNS.  A NULL entry, gates at different levels, an operand at a
+ * numerically higher level than the gates or a count out of range: SFHE_EINVAL.
+ * sfhe_group_counts: such calls whose tensors ran as fused launches
+ * (sfp_gate_tensor_cols) and as the composed generic prims since the last
+ * sfhe_op_stats reset (SFHE_GROUP_FUSED=0, read per call, composes; the results
+ * are bit-identical). */
+int sfhe_eval_gate_sum_many(sfhe_ctx* c, const sfhe_ct* const* q, size_t nq, const sfhe_ct* const* u, size_t ncols,
+                            sfhe_ct** outs);
+int sfhe_group_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
 /* nodes of the captured record sort (0 while none); sfhe_sorter_graph_nodes
  * keeps reporting the plain / stable sort's graph */
 int sfhe_sorter_records_graph_nodes(const sfhe_sorter* s, uint64_t* nodes);

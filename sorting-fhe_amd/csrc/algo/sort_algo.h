@@ -26,6 +26,8 @@
 // Several keys: constructRankLex ranks rows in (key_1, ...,
 // key_m, input index) order in one pass; sortRecordsLex / selectRecordsLex
 // place / select the keys and payload columns by it.
+// Grouping: groupAggregate gives every row the size of its
+// key's group, its number inside the group and the group's column sums.
 //
 // Engine-specific scheduling (identical slot values, fewer key switches):
 //   * baby-step rotations of one ciphertext share one hoisted ModUp;
@@ -124,6 +126,9 @@ inline int stableSortDepth(int N, const CompositeSignConfig& c) { return directS
 #define SFHE_LEX_KEYS 4
 inline int lexRankDepth(const CompositeSignConfig& c, int m) { return stableRankDepth(c) + (m - 1); }
 inline int lexSortDepth(int N, const CompositeSignConfig& c, int m) { return stableSortDepth(N, c) + (m - 1); }
+// Grouping by a key: 1 (mask) + sign + 1 (q = s^2) + 1 (the
+// gated product, or the index mask): the stable rank's levels and no placement.
+inline int groupDepth(const CompositeSignConfig& c) { return stableRankDepth(c); }
 
 // getSizeParameters' (depth, rotation keys) for N (reference :87-201);
 // nullptr when the reference has no entry.
@@ -663,6 +668,127 @@ class DirectSort : public SortBase<N> {
             mv.push_back(m_cc->MakeCKKSPackedPlaintext(c, 1, rank->GetLevel(), nullptr, N));
         })[0];
         return m_cc->EvalAdd(rank, base);
+    }
+
+    // ---- grouping by an encrypted key (COUNT(*), SUM(col), ROW_NUMBER() OVER
+    // (PARTITION BY key)) ----
+    struct GroupResult {
+        Ciphertext<DCRTPoly> count;              // count_r = #{j : key_j = key_r}
+        Ciphertext<DCRTPoly> index;              // index_r = #{j < r : key_j = key_r}; null unless asked for
+        std::vector<Ciphertext<DCRTPoly>> sums;  // sums[c]_r = sum of cols[c]_j over {j : key_j = key_r}
+    };
+    // M_b of the grouping's index: 1 where r + d >= N (j < r), d = bP + p; 0 for all of d = 0
+    std::vector<double> generateBeforeMask(int num_slots, int num_partition, int b) {
+        std::vector<double> v(num_slots, 0.0);
+        for (int p = 0; p < num_slots / N; ++p) {
+            const int d = b * num_partition + p;
+            for (int r = std::max(N - d, 0); r < N && d > 0; ++r) v[(size_t)p * N + r] = 1.0;
+        }
+        return v;
+    }
+    // In constructRankMode's slot layout (slot pN + r of batch b compares row r
+    // with row j = (r + d) mod N, d = bP + p), with s_b the composite sign of
+    // key_r - key_j, q_b = s_b^2 ("the keys differ") and u_bc column c's value at
+    // row j in the same layout:
+    //   count_r  = N - fold(sum_b q_b)_r                    at q's level
+    //   sum_cr   = fold(sum_b (1 - q_b) (.) u_bc)_r          one level below q
+    //   index_r  = r - fold(sum_b M_b (.) q_b)_r             one level below q
+    // fold: the rank's sum over the P partitions, then SetSlots(N).  No self
+    // offset here, whatever SFHE_SELF_OFFSET says: the self slot is a tie like
+    // any other, its gate 1 - q is 1 up to the square of the sign's noise, so
+    // the row's own value enters its sum with no special case.  Per batch on
+    // its lane: vecRotsOpt of the key and of every column (the columns share the
+    // key's masks), the sign, q_b, and M_b (.) q_b when the index is wanted;
+    // after the join ONE EvalGateSumMany for all batches and columns, the sums
+    // of q_b, and the folds.  The folds are the rank's doubling folds for every
+    // output: log2 P rotations each by amounts the rank already has keys for,
+    // where foldPartitions' radix-4 amounts would need keys of their own and
+    // sum inside a partition, not across them.  Depth groupDepth: the stable
+    // rank's.  Eager (no graph).  Precondition: two keys are equal or at least
+    // the sign configuration's resolution apart.
+    GroupResult groupAggregate(const Ciphertext<DCRTPoly>& keys, const std::vector<Ciphertext<DCRTPoly>>& cols,
+                               SignFunc SignFunc, SignConfig& Cfg, bool wantIndex, size_t maxCols) {
+        const size_t C = cols.size();
+        if (C > maxCols)
+            throw std::invalid_argument("group: " + std::to_string(C) + " payload columns (at most " +
+                                        std::to_string(maxCols) + ")");
+        for (const auto& c : cols)
+            if (c->GetLevel() != keys->GetLevel() || c->GetSlots() != keys->GetSlots())
+                throw std::invalid_argument("group: the key and the columns must be at one level and slot count");
+        const int need = (int)keys->GetLevel() + sfhe::groupDepth(Cfg.compos);
+        if ((int)m_cc->GetMultiplicativeDepth() < need)
+            throw OpenFHEException("group: needs multiplicative depth " + std::to_string(need) +
+                                   " (the stable rank's: the sign, its square and the gated product); the context has " +
+                                   std::to_string(m_cc->GetMultiplicativeDepth()));
+        const sfhe::RankLayout L(N, max_batch);
+        sfhe::PhaseTimer ph(m_cc);
+        std::vector<int> amounts(L.npRank);
+        for (int i = 0; i < L.npRank; ++i) amounts[i] = i;
+        auto pre = rot.rotateMany(keys, amounts);
+        for (auto& p : pre) p->SetSlots(L.S);
+        std::vector<std::vector<Ciphertext<DCRTPoly>>> preCols(C);
+        for (size_t c = 0; c < C; ++c) {
+            preCols[c] = rot.rotateMany(cols[c], amounts);
+            for (auto& p : preCols[c]) p->SetSlots(L.S);
+        }
+        ph.mark("group: baby rotations");
+
+        std::vector<Ciphertext<DCRTPoly>> q(L.B), mq(wantIndex ? L.B : 0);
+        std::vector<std::vector<Ciphertext<DCRTPoly>>> u(C, std::vector<Ciphertext<DCRTPoly>>(L.B));
+        const sfhe::BatchSplit split(m_cc, L.B);
+        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
+        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());
+        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
+            const int b = split.mine[i];
+            auto shifted = vecRotsOpt(pre, L.P, L.S, L.npRank, b);
+            for (size_t c = 0; c < C; ++c) u[c][b] = vecRotsOpt(preCols[c], L.P, L.S, L.npRank, b);
+            ph.mark("  group batch: vecRotsOpt");
+            auto dup = keys->Clone();
+            dup->SetSlots(L.S);
+            auto s = sign(m_cc->EvalSub(dup, shifted), m_cc, SignFunc, Cfg);
+            q[b] = m_cc->EvalMult(s, s);
+            if (wantIndex) {
+                const Plaintext& M = maskMemo({15, b, 0, (int)q[b]->GetLevel(), L.S}, [&](auto& v) {
+                    v.push_back(m_cc->MakeCKKSPackedPlaintext(generateBeforeMask(L.S, L.P, b), 1, q[b]->GetLevel(),
+                                                              nullptr, L.S));
+                })[0];
+                mq[b] = m_cc->EvalMult(q[b], M);
+            }
+            ph.mark("  group batch: sign + gate");
+        });
+        m_cc->JoinLanes();
+        split.gatherParts(m_cc, q);
+        if (wantIndex) split.gatherParts(m_cc, mq);
+        for (auto& col : u) split.gatherParts(m_cc, col);
+        ph.mark("group: batches");
+
+        auto fold = [&](Ciphertext<DCRTPoly> x) {
+            x->SetSlots(L.S);
+            for (int sft = L.S / 2; sft >= N; sft /= 2) m_cc->EvalAddInPlace(x, rot.rotate(x, sft));
+            x->SetSlots(N);
+            return x;
+        };
+        auto sumOf = [&](const std::vector<Ciphertext<DCRTPoly>>& parts) {
+            auto acc = parts[0]->Clone();
+            for (int b = 1; b < L.B; ++b) m_cc->EvalAddInPlace(acc, parts[b]);
+            return acc;
+        };
+        GroupResult out;
+        if (C) {
+            out.sums = m_cc->EvalGateSumMany(q, u);
+            for (auto& x : out.sums) x = fold(x);
+        }
+        ph.mark("group: gated sums + folds");
+        out.count = m_cc->EvalSub((double)N, fold(sumOf(q)));
+        if (wantIndex) {
+            auto before = fold(sumOf(mq));
+            const Plaintext& idx = maskMemo({16, 0, 0, (int)before->GetLevel(), N}, [&](auto& v) {
+                v.push_back(m_cc->MakeCKKSPackedPlaintext(generateIndexVector(), 1, before->GetLevel(), nullptr, N));
+            })[0];
+            out.index = m_cc->EvalSub(idx, before);
+        }
+        ph.mark("group: count + index");
+        return out;
     }
 
     // Rotates partition k = np*i + j of the masked inputs left by ib*P + k

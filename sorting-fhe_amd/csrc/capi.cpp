@@ -116,6 +116,8 @@ struct SorterBase {
     virtual std::vector<Ct> selectRecordsLex(const std::vector<Ct>& keys, const std::vector<Ct>& cols,
                                              const std::vector<int>& targets, const std::vector<bool>& desc,
                                              SignConfig& cfg) = 0;
+    // {count, index (null unless asked for), sums...}
+    virtual std::vector<Ct> group(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, bool wantIndex) = 0;
     virtual Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) = 0;
     virtual Ct hybrid(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk, int variant) = 0;
     virtual Ct place2N(const Ct& rank, const Ct& in) = 0;
@@ -181,6 +183,12 @@ struct Sorter : SorterBase {
                                      const std::vector<int>& targets, const std::vector<bool>& desc,
                                      SignConfig& cfg) override {
         return ds.selectRecordsLex(keys, cols, targets, desc, SignFunc::CompositeSign, cfg, SFHE_MAX_COLUMNS);
+    }
+    std::vector<Ct> group(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, bool wantIndex) override {
+        auto r = ds.groupAggregate(keys, cols, SignFunc::CompositeSign, cfg, wantIndex, SFHE_MAX_COLUMNS);
+        std::vector<Ct> out{r.count, r.index};
+        out.insert(out.end(), r.sums.begin(), r.sums.end());
+        return out;
     }
     Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) override {
         return ds.sort_hybrid1(in, SignFunc::CompositeSign, cfg, sk);
@@ -452,6 +460,14 @@ int sfhe_sumn_batch_counts(sfhe_ctx* c, uint64_t* batches, uint64_t* fallbacks) 
     auto s = c->cc->GetOpStats();
     *batches = s.sumn_batches;
     *fallbacks = s.sumn_fallbacks;
+    return SFHE_OK;
+}
+
+int sfhe_group_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
+    REQUIRE(c && fused && composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *fused = s.gate_fused;
+    *composed = s.gate_composed;
     return SFHE_OK;
 }
 
@@ -963,6 +979,72 @@ int sfhe_ct_relabel_scale(const sfhe_ct* ct, double factor, sfhe_ct** out) {
         auto x = ct->ct->Clone();
         x->scale *= factor;
         *out = wrap(x);
+    });
+}
+
+static_assert(SFHE_MAX_COLUMNS == CryptoContextImpl<DCRTPoly>::kGateMaxColumns,
+              "EvalGateSumMany's column limit is the record entry points'");
+
+int sfhe_group_params(uint32_t N, uint32_t* mult_depth, int32_t* rot, size_t cap, size_t* count) {
+    REQUIRE(validN(N), "N must be a power of two in [4, 1024]");
+    return guard([&] {
+        // the rank's amounts in the layout of the size table's ring (2^17): baby
+        // steps, giant steps, the batches' offsets and the partition folds.  A
+        // smaller ring uses a subset of them or composes its own from them.
+        const sfhe::RankLayout L((int)N, 1 << 16);
+        std::set<int> r;
+        for (int i = 1; i < L.npRank; ++i) r.insert(i);
+        for (int j = 1; j < L.P / L.npRank; ++j) r.insert(j * L.npRank);
+        for (int b = 1; b < L.B; ++b) r.insert(b * L.P);
+        for (int sft = L.S / 2; sft >= (int)N; sft /= 2) r.insert(sft);
+        if (mult_depth) *mult_depth = (uint32_t)sfhe::groupDepth(sfhe::defaultSignConfig((int)N));
+        if (count) *count = r.size();
+        size_t i = 0;
+        for (int v : r) {
+            if (i >= cap || !rot) break;
+            rot[i++] = v;
+        }
+    });
+}
+
+int sfhe_sorter_group(sfhe_sorter* s, const sfhe_ct* keys, const sfhe_ct* const* cols, size_t ncols, int want_index,
+                      int n, int dg, int df, sfhe_ct** count, sfhe_ct** index, sfhe_ct** sums_out) {
+    REQUIRE(s && keys && count && (!want_index || index) && (ncols == 0 || (cols && sums_out)), "null argument");
+    REQUIRE(ncols <= SFHE_MAX_COLUMNS, "column count out of range (0 .. SFHE_MAX_COLUMNS)");
+    for (size_t i = 0; i < ncols; ++i) REQUIRE(cols[i], "null column");
+    return guard([&] {
+        auto cfg = cfgOf(n, dg, df);
+        std::vector<Ct> in;
+        for (size_t i = 0; i < ncols; ++i) in.push_back(cols[i]->ct);
+        auto got = s->impl->group(keys->ct, in, cfg, want_index != 0);
+        *count = wrap(got[0]);
+        if (index) *index = want_index ? wrap(got[1]) : nullptr;
+        for (size_t i = 0; i < ncols; ++i) sums_out[i] = wrap(got[2 + i]);
+    });
+}
+
+int sfhe_eval_gate_sum_many(sfhe_ctx* c, const sfhe_ct* const* q, size_t nq, const sfhe_ct* const* u, size_t ncols,
+                            sfhe_ct** outs) {
+    REQUIRE(c && q && (ncols == 0 || (u && outs)), "null argument");
+    REQUIRE(nq >= 1, "no gates");
+    REQUIRE(ncols <= SFHE_MAX_COLUMNS, "column count out of range (0 .. SFHE_MAX_COLUMNS)");
+    for (size_t b = 0; b < nq; ++b) {
+        REQUIRE(q[b], "null gate");
+        REQUIRE(q[b]->ct->GetLevel() == q[0]->ct->GetLevel(), "the gates must be at one level");
+    }
+    for (size_t i = 0; i < ncols * nq; ++i) {
+        REQUIRE(u[i], "null operand");
+        REQUIRE(u[i]->ct->GetLevel() <= q[0]->ct->GetLevel(),
+                "the operands must have at least the gates' limbs (a level not above the gates')");
+    }
+    return guard([&] {
+        std::vector<Ct> qs;
+        for (size_t b = 0; b < nq; ++b) qs.push_back(q[b]->ct);
+        std::vector<std::vector<Ct>> us(ncols);
+        for (size_t k = 0; k < ncols; ++k)
+            for (size_t b = 0; b < nq; ++b) us[k].push_back(u[k * nq + b]->ct);
+        auto got = c->cc->EvalGateSumMany(qs, us);
+        for (size_t k = 0; k < ncols; ++k) outs[k] = wrap(got[k]);
     });
 }
 

@@ -3309,6 +3309,122 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalLexStep(const Ciphertext<D
     return SfheInternal::traced(this, r, "EvalLexStep");
 }
 
+// Per column one tensor at q's level over all batches: every (kr - q_b) u_bc
+// carries Delta_q Delta_u, so the batches' tensors are summed as integers
+// before the column's single relinearisation and rescale.  The relinearisations
+// of the columns run one by one: the engine's batched forms (multRelinRescaleMany,
+// EvalMultSumMany) take operand pairs and form the tensor inside the key
+// switch's passes, which a sum over batches with shared gates does not fit.
+std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalGateSumMany(
+    const std::vector<Ciphertext<DCRTPoly>>& q, const std::vector<std::vector<Ciphertext<DCRTPoly>>>& u) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    const size_t nb = q.size(), nc = u.size();
+    if (!nb) SFHE_THROW("EvalGateSumMany: no gates");
+    if (nc > kGateMaxColumns)
+        SFHE_THROW("EvalGateSumMany: " + std::to_string(nc) + " columns (at most " + std::to_string(kGateMaxColumns) +
+                   ")");
+    if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalGateSumMany");
+    for (const auto& x : q) {
+        if (!x) SFHE_THROW("EvalGateSumMany: null gate");
+        SfheInternal::deps(s, {&x});
+    }
+    const uint32_t level = q[0]->level, ell = s->ellOf(level);
+    uint32_t slots = q[0]->slots;
+    for (const auto& x : q) {
+        if (x->level != level || x->scale != q[0]->scale)
+            SFHE_THROW("EvalGateSumMany: the gates must be at one level and one scale");
+        slots = std::max(slots, x->slots);
+    }
+    for (const auto& col : u) {
+        if (col.size() != nb) SFHE_THROW("EvalGateSumMany: every column needs one operand per gate");
+        for (const auto& x : col) {
+            if (!x) SFHE_THROW("EvalGateSumMany: null operand");
+            SfheInternal::deps(s, {&x});
+            if (x->level > level)
+                SFHE_THROW("EvalGateSumMany: the operands must have at least the gates' limbs (level " +
+                           std::to_string(x->level) + " against the gates' " + std::to_string(level) + ")");
+            if (x->scale != col[0]->scale) SFHE_THROW("EvalGateSumMany: a column's operands must be at one scale");
+            slots = std::max(slots, x->slots);
+        }
+    }
+    std::vector<Ciphertext<DCRTPoly>> out(nc);
+    if (!nc) return out;
+    if (ell < 2) SFHE_THROW("no levels left (the gated sum consumes one level)");
+    // an operand's rows over q's limbs: a prefix of its own, gathered where its
+    // rows are dealt over the ranks and q's level is replicated (EvalLexStep)
+    std::vector<DeviceBufferPtr> keep;
+    auto rowsOf = [&](const Ciphertext<DCRTPoly>& x, const uint64_t*& x0, const uint64_t*& x1) {
+        x0 = x->c0;
+        x1 = x->c1;
+        if (s->shardAt(s->ellOf(x->level)) && !s->shardAt(ell)) {
+            keep.push_back(SfheInternal::gatherRows(s, x->c0, x->c1, ell));
+            x0 = keep.back()->ptr;
+            x1 = x0 + (size_t)ell * s->n;
+        }
+    };
+    std::vector<const uint64_t*> q0(nb), q1(nb), u0(nc * nb), u1(nc * nb);
+    for (size_t b = 0; b < nb; ++b) {
+        q0[b] = q[b]->c0;
+        q1[b] = q[b]->c1;
+    }
+    for (size_t c = 0; c < nc; ++c)
+        for (size_t b = 0; b < nb; ++b) rowsOf(u[c][b], u0[c * nb + b], u1[c * nb + b]);
+    const auto kr = SfheInternal::constResidues(s, q[0]->scale, ell);
+    const size_t pw = s->polyWords(level);
+    const sfp_limbs m = s->qmap(ell);
+    auto t = s->alloc(3 * pw * nc);
+    std::vector<uint64_t*> d0(nc), d1(nc), d2(nc);
+    for (size_t c = 0; c < nc; ++c) {
+        d0[c] = t->ptr + 3 * pw * c;
+        d1[c] = d0[c] + pw;
+        d2[c] = d1[c] + pw;
+    }
+    const char* knob = std::getenv("SFHE_GROUP_FUSED");  // (read per call: tests switch it)
+    const bool fused = sfp_gate_tensor_cols && !(knob && *knob == '0') && !s->shardAt(ell) && nb <= SFP_GATE_MAX_B &&
+                       sfp_gate_tensor_cols(s->dev, d0.data(), d1.data(), d2.data(), q0.data(), q1.data(), u0.data(),
+                                            u1.data(), kr.data(), (uint32_t)nb, (uint32_t)nc, m) == 0;
+    if (fused) {
+        s->stats.gate_fused++;
+    } else {  // the same integers from the generic prims: a_b = kr - q_b, then the tensors summed over b
+        auto a = s->alloc(5 * pw);
+        uint64_t* a0 = a->ptr;
+        uint64_t* a1 = a0 + pw;
+        uint64_t* t0 = a1 + pw;
+        uint64_t* t1 = t0 + pw;
+        uint64_t* t2 = t1 + pw;
+        for (size_t b = 0; b < nb; ++b) {
+            sfp_neg(s->dev, a0, q0[b], m);
+            sfp_neg(s->dev, a1, q1[b], m);
+            sfp_add_const(s->dev, a0, a0, kr.data(), m);
+            for (size_t c = 0; c < nc; ++c) {
+                if (b == 0) {
+                    sfp_tensor(s->dev, d0[c], d1[c], d2[c], a0, a1, u0[c * nb], u1[c * nb], m);
+                    continue;
+                }
+                sfp_tensor(s->dev, t0, t1, t2, a0, a1, u0[c * nb + b], u1[c * nb + b], m);
+                sfp_add(s->dev, d0[c], d0[c], t0, m);
+                sfp_add(s->dev, d1[c], d1[c], t1, m);
+                sfp_add(s->dev, d2[c], d2[c], t2, m);
+            }
+        }
+        s->stats.gate_composed++;
+    }
+    s->stats.constmult += nb;
+    s->stats.tensor += nb * nc;
+    // the fused form, modelled: per tile of CT columns 2 nb (1 + CT) rows read and 3 CT written per limb
+    for (size_t c = 0; c < nc; c += 2) {
+        const double ct = (double)std::min<size_t>(2, nc - c);
+        s->countBytes((2.0 * nb * (1.0 + ct) + 3.0 * ct) * ell * s->n * 8);
+    }
+    for (size_t c = 0; c < nc; ++c) {
+        auto r = SfheInternal::relinRescale(this, d0[c], d1[c], d2[c], level, slots);
+        r->scale = q[0]->scale * u[c][0]->scale / (double)s->primes[ell - 1];
+        out[c] = SfheInternal::traced(this, r, "EvalGateSumMany");
+    }
+    return out;
+}
+
 std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultMany(
     const std::vector<Ciphertext<DCRTPoly>>& a0, const std::vector<Ciphertext<DCRTPoly>>& b0) {
     OpLock g(st.get());

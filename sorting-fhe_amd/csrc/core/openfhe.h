@@ -409,6 +409,23 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     // lex_composed count the calls of each kind.
     Ciphertext<DCRTPoly> EvalLexStep(const Ciphertext<DCRTPoly>& v, const Ciphertext<DCRTPoly>& q,
                                      const Ciphertext<DCRTPoly>& u);
+    // Engine extension (the grouping's gated column sums):
+    // out[c] = sum_b (1 - q[b]) (.) u[c][b], relinearised ONCE per column, one
+    // level below q.  The B gates q[b] share one level and one scale and serve
+    // all C <= kGateMaxColumns columns; column c's operands u[c][b] share one
+    // scale and have at least q's limbs (a numerically lower or equal level):
+    // they are read over q's limbs.  The constant 1 enters as the residues of
+    // Delta_q, so every product carries Delta_q Delta_u and the sum is exact;
+    // the result's scale field holds Delta_q Delta_u / q_dropped (EvalLexStep).
+    // The tensors of all batches and columns are one launch per tile of two
+    // columns where the backend has prims.h sfp_gate_tensor_cols and B <=
+    // SFP_GATE_MAX_B; elsewhere (the C oracle, SFHE_GROUP_FUSED=0 -- read per
+    // call --, a level whose rows are dealt over ranks, more batches, or the
+    // prim declining) the generic prims compose the same integers.  OpStats
+    // gate_fused / gate_composed count the calls of each kind.
+    static constexpr size_t kGateMaxColumns = 8;
+    std::vector<Ciphertext<DCRTPoly>> EvalGateSumMany(const std::vector<Ciphertext<DCRTPoly>>& q,
+                                                      const std::vector<std::vector<Ciphertext<DCRTPoly>>>& u);
     // Engine extension: EvalMult(a_i, b_i) for independent pairs, each formed
     // canonically (rescaled: the values a lazy product takes when its
     // consumer needs the canonical form); pairs at one level run as batched
@@ -786,6 +803,7 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         // remainder chains of the Chebyshev evaluator that fell outside EvalMultSum's conditions
         // and ran as separate products and sums
         uint64_t sumn_batches = 0, sumn_fallbacks = 0;
+        uint64_t gate_fused = 0, gate_composed = 0;  // EvalGateSumMany calls: tensors fused / composed of generic prims
     };
     OpStats GetOpStats() const;
     void ResetOpStats();
@@ -868,7 +886,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 14
+#define SFHE_FACADE_ABI_VERSION 15
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

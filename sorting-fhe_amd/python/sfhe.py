@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "sfhe_eval_mult_sum2", "sfhe_dot_counts",
     "sfhe_eval_mult_sum", "sfhe_sumn_counts",
     "sfhe_eval_mult_sum_many", "sfhe_sumn_batch_counts", "sfhe_ct_relabel_scale",
+    "sfhe_group_params", "sfhe_sorter_group", "sfhe_eval_gate_sum_many", "sfhe_group_counts",
 ]
 
 MAX_COLUMNS = 8  # SFHE_MAX_COLUMNS
@@ -219,6 +220,10 @@ _SIGS = {
     "sfhe_eval_mult_sum_many": (C.c_int, [_VP, _PVP, _PVP, C.POINTER(C.c_size_t), C.c_size_t, _PVP, _PVP]),
     "sfhe_sumn_batch_counts": (C.c_int, [_VP, _PU64, _PU64]),
     "sfhe_ct_relabel_scale": (C.c_int, [_VP, C.c_double, _PVP]),
+    "sfhe_group_params": (C.c_int, [_U32, _PU32, _PI32, _SZ, _PSZ]),
+    "sfhe_sorter_group": (C.c_int, [_VP, _VP, _PVP, _SZ, C.c_int, C.c_int, C.c_int, C.c_int, _PVP, _PVP, _PVP]),
+    "sfhe_eval_gate_sum_many": (C.c_int, [_VP, _PVP, _SZ, _PVP, _SZ, _PVP]),
+    "sfhe_group_counts": (C.c_int, [_VP, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -587,6 +592,28 @@ class Engine:
         self._chk(self.lib.sfhe_dot_counts(self.ctx, C.byref(f), C.byref(c)))
         return f.value, c.value
 
+    def gate_sum_many(self, qs, us):
+        """[sum_b (1 - qs[b]) * us[c][b] for each column c], one level below the gates (one
+        relinearisation and one rescale per column): the grouping's gated column sums.  The
+        gates share one level; operands may sit at a numerically lower level."""
+        qs, us = list(qs), [list(col) for col in us]
+        for col in us:
+            if len(col) != len(qs):
+                raise SfheError("sfhe error -1: every column needs one operand per gate")
+        qh = (_VP * max(len(qs), 1))(*[q.h if q is not None else None for q in qs])
+        flat = [x.h if x is not None else None for col in us for x in col]
+        uh = (_VP * max(len(flat), 1))(*flat)
+        outs = (_VP * max(len(us), 1))()
+        self._chk(self.lib.sfhe_eval_gate_sum_many(self.ctx, qh, len(qs), uh, len(us), outs))
+        return [Ct(self, C.c_void_p(outs[i])) for i in range(len(us))]
+
+    def group_counts(self):
+        """(fused, composed) gate_sum_many calls (Sorter.group's included) since the last
+        op_stats reset."""
+        f, c = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_group_counts(self.ctx, C.byref(f), C.byref(c)))
+        return f.value, c.value
+
     def lex_counts(self):
         """(fused, composed) lex_step tensors (rank_lex's included) since the last op_stats reset."""
         f, c = C.c_uint64(), C.c_uint64()
@@ -906,6 +933,22 @@ class Sorter:
         """The first k rows in (keys, input index) order."""
         return self.select_records_lex(keys, cts, list(range(k)), descending, **kw)
 
+    # -- GROUP BY key --
+    def group(self, keys: Ct, cts=(), index: bool = False, n: int = 3, dg: int = 2, df: int = 2):
+        """COUNT(*), SUM(col) and ROW_NUMBER() over the rows sharing a key, in input order:
+        {"count": slot r = rows with row r's key, "index": slot r = rows before r with its key
+        (None unless index=True), "sums": [slot r = column's sum over the rows with r's key]}.
+        The context needs group_params' depth for the sign configuration (SfheError otherwise);
+        no placement is evaluated."""
+        cts = list(cts)
+        cs = (_VP * max(len(cts), 1))(*[c.h if c is not None else None for c in cts])
+        cnt, idx = _VP(), _VP()
+        outs = (_VP * max(len(cts), 1))()
+        self.eng._chk(self.eng.lib.sfhe_sorter_group(self.h, keys.h, cs, len(cts), int(bool(index)), n, dg, df,
+                                                     C.byref(cnt), C.byref(idx), outs))
+        return {"count": Ct(self.eng, cnt), "index": Ct(self.eng, idx) if index else None,
+                "sums": [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cts))]}
+
     def top_k(self, ct: Ct, k: int, largest: bool = False, **kw) -> Ct:
         """The k smallest values in ascending order (largest: the k largest, descending)."""
         return self.select(ct, [self.N - 1 - i for i in range(k)] if largest else list(range(k)), **kw)
@@ -982,6 +1025,20 @@ def select_params(N: int, backend: str = "hip"):
         raise SfheError(lib.sfhe_last_error().decode())
     buf = (C.c_int32 * cnt.value)()
     lib.sfhe_select_params(N, None, buf, cnt.value, None)
+    return depth.value, list(buf)
+
+
+def group_params(N: int, backend: str = "hip"):
+    """(depth, rotations) for Sorter.group with N's default sign configuration: the stable
+    rank's depth (no placement) and the rank's rotation amounts."""
+    lib = load(backend)
+    depth = C.c_uint32()
+    cnt = C.c_size_t()
+    rc = lib.sfhe_group_params(N, C.byref(depth), None, 0, C.byref(cnt))
+    if rc != SFHE_OK:
+        raise SfheError(lib.sfhe_last_error().decode())
+    buf = (C.c_int32 * cnt.value)()
+    lib.sfhe_group_params(N, None, buf, cnt.value, None)
     return depth.value, list(buf)
 
 
