@@ -391,7 +391,16 @@ _SIGS = {
     "sfp_mult_relin_rescale_add": ("i", "ppppppuuuupppppppppppip"),
     "sfp_const_terms_rescale": ("i", "pzupu"),
     "sfp_sample_uniform": (None, "pLq"), "sfp_load_i64": (None, "ppL"), "sfp_sample_small": ("i", "pzuppL"),
+    "sfp_modup_prepare": (None, "puuu"),
+    # merged launches: batches, stacked regions, lanes, events, graphs
+    "sfp_batch_begin": ("i", "u"), "sfp_batch_lane": (None, "u"), "sfp_batch_end": (None, ""),
+    "sfp_stack_begin": (None, ""), "sfp_stack_end": (None, ""), "sfp_stack_stats": (None, "pp"),
+    "sfp_lanes": ("i", ""), "sfp_set_lane": (None, "i"), "sfp_get_lane": ("i", ""), "sfp_lane_wait": (None, "ii"),
+    "sfp_event_record": ("p", ""), "sfp_event_wait": (None, "p"), "sfp_event_free": (None, "p"),
+    "sfp_capture_begin": ("i", ""), "sfp_capture_end": ("p", ""), "sfp_graph_launch": (None, "p"),
+    "sfp_graph_destroy": (None, "p"), "sfp_graph_nodes": ("z", "p"),
 }
+_NO_DEV = {"sfp_graph_nodes"}  # (take no device handle)
 
 
 def _host(a):
@@ -422,6 +431,22 @@ class Dev:
     def has(self, name):
         return hasattr(self.lib, name)
 
+    def merges(self):
+        """Whether this library merges launches at all (the oracle's regions are no-ops)."""
+        name = self.lib.sfp_backend_name
+        name.restype, name.argtypes = C.c_char_p, []
+        return not name().startswith(b"oracle")
+
+    def stats(self):
+        """sfp_stack_stats: (launches issued merged, launches issued alone) so far."""
+        m, s = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+        self.call("sfp_stack_stats", m, s)
+        return int(m[0]), int(s[0])
+
+    def stats_delta(self):
+        """with D.stats_delta() as got: ...  -- got() is the (merged, single) delta of the block."""
+        return _StatsDelta(self)
+
     def check(self):
         e = self.lib.sfp_last_error(self.d)
         assert e is None, e
@@ -432,10 +457,10 @@ class Dev:
             f = getattr(self.lib, name)
             res, codes = _SIGS[name]
             f.restype = _T[res] if res else None
-            f.argtypes = [C.c_void_p] + [_T[c] for c in codes]
+            f.argtypes = ([] if name in _NO_DEV else [C.c_void_p]) + [_T[c] for c in codes]
             self._fn[name] = f
         args = [_host(a) if isinstance(a, np.ndarray) else a for a in args]
-        r = f(self.d, *args)
+        r = f(*args) if name in _NO_DEV else f(self.d, *args)
         if name not in ("sfp_free", "sfp_destroy"):
             self.check()
         return r
@@ -474,6 +499,20 @@ class Dev:
     @staticmethod
     def ptrs(ps):
         return np.array([int(p) for p in ps], dtype=np.uint64)  # a host array of device pointers
+
+
+class _StatsDelta:
+    def __init__(self, D):
+        self.D = D
+
+    def __enter__(self):
+        self.before = self.D.stats()
+        self.after = None
+        return lambda: tuple(a - b for a, b in zip(self.after or self.D.stats(), self.before))
+
+    def __exit__(self, *exc):
+        self.after = self.D.stats()
+        return False
 
 
 _devs = {}
