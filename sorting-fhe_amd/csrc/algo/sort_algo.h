@@ -28,6 +28,12 @@
 // place / select the keys and payload columns by it.
 // Grouping: groupAggregate gives every row the size of its
 // key's group, its number inside the group and the group's column sums.
+// What these methods share is written once: runBatches (the batches over
+// lanes and batch groups), sumOverPartitions (batch sum and folds),
+// sfhe::SincIndicator (the placements' and selections' indicator), MemoTag and
+// memoPlain with the entries' builders, lexRank (the stable rank is its
+// one-key case) and runCached (the graph protocol of the plain, the stable
+// and the record sort).
 //
 // Engine-specific scheduling (identical slot values, fewer key switches):
 //   * baby-step rotations of one ciphertext share one hoisted ModUp;
@@ -228,7 +234,7 @@ inline bool stackBatches() {  // (read per sort phase: tests switch it)
 }
 
 // Placement evaluates the doubled sinc in the rebased variable (on unless
-// SFHE_SINC_REBASE=0; see rotationIndexCheckN).
+// SFHE_SINC_REBASE=0; see SincIndicator).
 inline bool sincRebase() {
     const char* v = std::getenv("SFHE_SINC_REBASE");
     return !v || *v != '0';
@@ -281,6 +287,41 @@ class PhaseTimer {
     std::mutex m_mu;
     std::chrono::steady_clock::time_point m_t;
     CryptoContextImpl<DCRTPoly>::OpStats m_s;
+};
+
+// The indicator of both placements and both selections, one value per call:
+// D(d / 2N) of an integer offset d in (-2N, N) is 1 at d = 0 and 0 at the
+// other integers.  The doubled sinc p is evaluated on y = (4z + 1)/3, its
+// argument's range z = d/2N in (-1, 1/2) mapped onto [-1, 1]: the same
+// polynomial (re-expanded, sfhe::rebasedChebyshev), the same levels, but the
+// hits z = 0 land at y = 1/3 instead of an extremum of every giant step
+// T_{2^i}, which cuts the CKKS noise of the placement ~2^8-fold (DESIGN.md
+// §2).  SFHE_SINC_REBASE=0 evaluates p(z) as the reference.
+struct SincIndicator {
+    int N;
+    bool rebase;
+    const std::vector<double>& coeffs;
+    double zmul, zadd;
+    uint32_t psDepth;  // the PS depth of the reference's series (level tables)
+    explicit SincIndicator(int N)
+        : N(N), rebase(sincRebase()),
+          coeffs(rebase ? rebasedChebyshev(doubledSincCoefficients(N), -1.0, 0.5) : doubledSincCoefficients(N)),
+          zmul(rebase ? 4.0 / 3.0 : 1.0), zadd(rebase ? 1.0 / 3.0 : 0.0),
+          psDepth(lbcrypto::ChebyshevPSDepth((uint32_t)doubledSincCoefficients(N).size() - 1)) {}
+    // hit = D(diff / 2N), diff the ciphertext of the offsets d
+    Ciphertext<DCRTPoly> hit(const CryptoContext<DCRTPoly>& cc, const Ciphertext<DCRTPoly>& diff,
+                             PhaseTimer& ph) const {
+        auto z = cc->EvalMult(diff, zmul / N / 2);
+        if (rebase) z = cc->EvalAdd(z, zadd);
+        ph.mark("  indicator: z");
+        auto h = cc->EvalChebyshevSeriesPS(z, coeffs, -1, 1);
+        // the rebased series may be shorter (tiny tail terms dropped) and so
+        // shallower: consume exactly the reference's PS depth (level tables)
+        const uint32_t psLevel = z->GetLevel() + psDepth;
+        if (h->GetLevel() < psLevel) h = cc->AdjustLevel(h, psLevel);
+        ph.mark("  indicator: sinc PS");
+        return h;
+    }
 };
 }  // namespace sfhe
 
@@ -392,6 +433,27 @@ class DirectSort : public SortBase<N> {
     // The 0/1 masks depend only on (N, layout, batch, giant step, level), so
     // their Plaintexts (and with them the device encodings) are kept across
     // sorts: repeated sorts skip mask generation, rotation and re-encoding.
+    // A memo key is {tag, a, b, level, slots}; the tags' values are part of
+    // the keys (a, b in brackets).
+    enum MemoTag : int {
+        kRankMasks = 0,          // vecRotsOpt's giant-step masks [is, j]
+        kBlindMasks = 1,         // blindRotationMasks [0, i]
+        kIndexVector = 2,        // indexPlain
+        kCheckingVector = 3,     // checkingPlain [b]
+        kColumnMask = 4,         // sumColumnsToTarget [M, column]
+        kRowMask = 5,            // transposeColumnTarget [M, row]
+        kHybrid1Sub = 6,         // matrixPlacement's subMask, hybrid I [b]
+        kSelfOffset = 7,         // selfOffsetPlain
+        kHybridSub = 8,          // matrixPlacement's subMask, hybrid and hybrid II [b]
+        kBlindMasks2N = 9,       // blindRotationOpt2N [0, i]
+        kCheckingVector2N = 10,  // rotationIndexCheck2N [b]
+        kTieWeights = 11,        // tieWeightsPlain [b]
+        kRankBase = 12,          // rankBasePlain [self offset on]
+        kTargets = 13,           // targetPlain [b, target list]
+        kMoveMasks = 14,         // moveMasks [target list, 1024 b + g]
+        kBeforeMask = 15,        // groupAggregate's M_b [b]
+        kGroupIndex = 16         // groupAggregate's index vector
+    };
     std::map<std::array<int, 5>, std::vector<Plaintext>> m_masks;
     std::mutex m_masksMu;  // the batches' host threads share the memo
     // Returns the memoised plaintexts for `key`, building them once with
@@ -427,6 +489,80 @@ class DirectSort : public SortBase<N> {
             2);
         return {vs.begin(), vs.end()};
     }
+    // The memo entry {tag, a, b, level, slots} that holds one packed plaintext,
+    // encoded from slotVector() the first time.
+    template <class F>
+    const Plaintext& memoPlain(MemoTag tag, int a, int b, uint32_t level, int slots, F&& slotVector) {
+        return maskMemo({tag, a, b, (int)level, slots}, [&](auto& v) {
+            v.push_back(m_cc->MakeCKKSPackedPlaintext(slotVector(), 1, level, nullptr, slots));
+        })[0];
+    }
+    // [0, 1, ..., N-1] over N slots (the grouping keeps an entry of its own)
+    const Plaintext& indexPlain(uint32_t level, MemoTag tag = kIndexVector) {
+        return memoPlain(tag, 0, 0, level, N, [&] { return generateIndexVector(); });
+    }
+    // kSelfOffset on the self comparison's slots: partition 0 of batch 0
+    const Plaintext& selfOffsetPlain(uint32_t level, int num_slots) {
+        return memoPlain(kSelfOffset, 0, 0, level, num_slots, [&] {
+            std::vector<double> o(num_slots, 0.0);
+            std::fill(o.begin(), o.begin() + N, sfhe::kSelfOffset);
+            return o;
+        });
+    }
+    const Plaintext& tieWeightsPlain(int b, uint32_t level, const sfhe::RankLayout& L) {
+        return memoPlain(kTieWeights, b, 0, level, L.S, [&] { return generateTieWeights(L.S, L.P, b); });
+    }
+    // The stable rank's constants: the terms' 1/2 + w sum to r over d != 0 and
+    // the self slots give 1/2, less the self comparison (step(selfOffset) = 1,
+    // the reference's step(0) = 1/2).
+    const Plaintext& rankBasePlain(uint32_t level, bool offsetSelf) {
+        return memoPlain(kRankBase, offsetSelf ? 1 : 0, 0, level, N, [&] {
+            const double self = 0.5 - (offsetSelf ? 1.0 : 0.5);
+            std::vector<double> c(N);
+            for (int r = 0; r < N; ++r) c[r] = r + self;
+            return c;
+        });
+    }
+    const Plaintext& checkingPlain(int b, uint32_t level, const sfhe::RankLayout& L) {
+        return memoPlain(kCheckingVector, b, 0, level, L.S, [&] { return generateCheckingVectorN(L.S, b * L.P); });
+    }
+
+    // [0, 1, ..., n-1]: the baby steps' rotation amounts
+    static std::vector<int> babySteps(int n) {
+        std::vector<int> amounts(n);
+        for (int i = 0; i < n; ++i) amounts[i] = i;
+        return amounts;
+    }
+    // the rank's baby-step rotations of one column, at S slots
+    std::vector<Ciphertext<DCRTPoly>> rankBabyRotations(const Ciphertext<DCRTPoly>& x, const sfhe::RankLayout& L) {
+        auto pre = rot.rotateMany(x, babySteps(L.npRank));
+        for (auto& p : pre) p->SetSlots(L.S);
+        return pre;
+    }
+
+    // Runs body(b) for the batches b < count of one phase.  The batches are
+    // independent: each runs on its own lane (stream), and over batch groups
+    // on its own GPU group (this group's share only).  The caller gathers its
+    // parts with the split that is returned.
+    template <class F>
+    sfhe::BatchSplit runBatches(int count, F&& body) {
+        sfhe::BatchSplit split(m_cc, count);
+        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
+        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());  // (one batch: no region, the PS may open its own)
+        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) { body(split.mine[i]); });
+        m_cc->JoinLanes();
+        return split;
+    }
+    // The end of every batched phase: the parts added to `acc` in batch order,
+    // then the sum over the partitions (period N inside S slots) by doubling
+    // rotations, and N slots again.
+    Ciphertext<DCRTPoly> sumOverPartitions(Ciphertext<DCRTPoly> acc, const std::vector<Ciphertext<DCRTPoly>>& parts,
+                                           int S) {
+        for (const auto& p : parts) m_cc->EvalAddInPlace(acc, p);
+        for (int s = S / 2; s >= N; s /= 2) m_cc->EvalAddInPlace(acc, rot.rotate(acc, s));
+        acc->SetSlots(N);
+        return acc;
+    }
 
     // The giant steps' rotations is*P + j*np are applied as one rotation by
     // is*P of the sum over j of rotations by j*np (rotations are linear), and
@@ -437,7 +573,7 @@ class DirectSort : public SortBase<N> {
         std::vector<std::array<int, 5>> keys;
         std::vector<int> steps;
         for (int j = 0; j < num_partition / np; ++j) {
-            keys.push_back({0, is, j, (int)pre[0]->GetLevel(), num_slots});
+            keys.push_back({kRankMasks, is, j, (int)pre[0]->GetLevel(), num_slots});
             steps.push_back(j * np);
         }
         const auto masks = maskMemoMany(keys, np, [&](size_t j, int i) {
@@ -453,9 +589,38 @@ class DirectSort : public SortBase<N> {
         return rot.rotate(rot.rotateSum(giants, steps), is * num_partition);
     }
 
+    // The self comparison x_r vs x_r sits in partition 0 of batch 0 (shift 0).
+    // Its difference is pure CKKS noise at the composite sign's steepest
+    // point (slope ~ 4.5^dg), which made it the largest term of the rank
+    // error (~1e-4 at N=256).  The engine moves those N slots' difference to
+    // +selfOffset (an exact plaintext addition, selfOffsetPlain), where the
+    // sign is saturated: the term contributes 1 instead of 1/2 and the final
+    // correction is -1 instead of the reference's -1/2 (:503-504).  Same rank
+    // up to the sign's approximation error; DESIGN.md §2.
     Ciphertext<DCRTPoly> constructRank(const Ciphertext<DCRTPoly>& input_array, SignFunc SignFunc,
                                        SignConfig& Cfg) {
-        return constructRankMode(input_array, SignFunc, Cfg, false);
+        const sfhe::RankLayout L(N, max_batch);
+        sfhe::PhaseTimer ph(m_cc);
+        const auto pre = rankBabyRotations(input_array, L);
+        ph.mark("rank: baby rotations");
+        auto rank = this->getZero()->Clone();
+        rank->SetSlots(L.S);
+        const bool offsetSelf = sfhe::selfOffset();
+        std::vector<Ciphertext<DCRTPoly>> parts(L.B);
+        const auto split = runBatches(L.B, [&](int b) {
+            auto shifted = vecRotsOpt(pre, L.P, L.S, L.npRank, b);
+            ph.mark("  rank batch: vecRotsOpt");
+            auto dup = input_array->Clone();
+            dup->SetSlots(L.S);
+            if (b == 0 && offsetSelf) dup = m_cc->EvalAdd(dup, selfOffsetPlain(dup->GetLevel(), L.S));
+            parts[b] = comp.compare(m_cc, dup, shifted, SignFunc, Cfg);
+            ph.mark("  rank batch: compare");
+        });
+        split.gatherParts(m_cc, parts);
+        rank = sumOverPartitions(rank, parts, L.S);
+        ph.mark("rank: batch sum + folds");
+        // remove the self comparison: step(selfOffset) = 1 (reference: step(0) = 1/2)
+        return m_cc->EvalSub(rank, offsetSelf ? 1.0 : 0.5);
     }
 
     // The stable ascending rank #{j : x_j < x_r} + #{j < r : x_j = x_r}: correct
@@ -467,7 +632,8 @@ class DirectSort : public SortBase<N> {
     // counts a tie exactly when j < r.  Per batch the variable part
     // s (.) (W (.) s + 1/2), W = -w, is one EvalTieTerm; the constants
     // 1/2 + w sum to r over d != 0 and are added once after the fold, with the
-    // self comparison's correction.  One level more than constructRank.
+    // self comparison's correction.  One level more than constructRank.  It is
+    // the lexicographic rank by one ascending key (lexRank).
     // Precondition: two inputs are equal or at least the sign configuration's
     // resolution apart (1/N for the default configurations).
     Ciphertext<DCRTPoly> constructRankStable(const Ciphertext<DCRTPoly>& input_array, SignFunc SignFunc,
@@ -477,7 +643,7 @@ class DirectSort : public SortBase<N> {
             throw OpenFHEException("stable rank: needs multiplicative depth " + std::to_string(need) +
                                    " (one level more than the plain rank for the tie term); the context has " +
                                    std::to_string(m_cc->GetMultiplicativeDepth()));
-        return constructRankMode(input_array, SignFunc, Cfg, true);
+        return lexRank({input_array}, {false}, SignFunc, Cfg);
     }
 
     // W = -w of batch b (constructRankStable)
@@ -491,82 +657,6 @@ class DirectSort : public SortBase<N> {
         return v;
     }
 
-    Ciphertext<DCRTPoly> constructRankMode(const Ciphertext<DCRTPoly>& input_array, SignFunc SignFunc,
-                                           SignConfig& Cfg, bool stable) {
-        const sfhe::RankLayout L(N, max_batch);
-        sfhe::PhaseTimer ph(m_cc);
-        std::vector<int> amounts(L.npRank);
-        for (int i = 0; i < L.npRank; ++i) amounts[i] = i;
-        auto pre = rot.rotateMany(input_array, amounts);
-        for (auto& p : pre) p->SetSlots(L.S);
-        ph.mark("rank: baby rotations");
-
-        auto rank = this->getZero()->Clone();
-        rank->SetSlots(L.S);
-        // The self comparison x_r vs x_r sits in partition 0 of batch 0
-        // (shift 0).  Its difference is pure CKKS noise at the composite
-        // sign's steepest point (slope ~ 4.5^dg), which made it the largest
-        // term of the rank error (~1e-4 at N=256).  The engine moves those N
-        // slots' difference to +selfOffset (an exact plaintext addition), where
-        // the sign is saturated: the term contributes 1 instead of 1/2 and the
-        // final correction is -1 instead of the reference's -1/2 (:503-504).
-        // Same rank up to the sign's approximation error; DESIGN.md §2.
-        const bool offsetSelf = sfhe::selfOffset();
-        // the batches are independent: each runs on its own lane (stream),
-        // and over batch groups on its own GPU group
-        std::vector<Ciphertext<DCRTPoly>> parts(L.B);
-        const sfhe::BatchSplit split(m_cc, L.B);
-        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
-        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());  // (one batch: no region, the PS may open its own)
-        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
-            const int b = split.mine[i];
-            auto shifted = vecRotsOpt(pre, L.P, L.S, L.npRank, b);
-            ph.mark("  rank batch: vecRotsOpt");
-            auto dup = input_array->Clone();
-            dup->SetSlots(L.S);
-            if (b == 0 && offsetSelf) {
-                const Plaintext& off = maskMemo({7, 0, 0, (int)dup->GetLevel(), L.S}, [&](auto& v) {
-                    std::vector<double> o(L.S, 0.0);
-                    std::fill(o.begin(), o.begin() + N, sfhe::kSelfOffset);
-                    v.push_back(m_cc->MakeCKKSPackedPlaintext(o, 1, dup->GetLevel(), nullptr, L.S));
-                })[0];
-                dup = m_cc->EvalAdd(dup, off);
-            }
-            if (stable) {
-                auto s = sign(m_cc->EvalSub(dup, shifted), m_cc, SignFunc, Cfg);
-                const Plaintext& W = maskMemo({11, b, 0, (int)s->GetLevel(), L.S}, [&](auto& v) {
-                    v.push_back(m_cc->MakeCKKSPackedPlaintext(generateTieWeights(L.S, L.P, b), 1, s->GetLevel(),
-                                                              nullptr, L.S));
-                })[0];
-                parts[b] = m_cc->EvalTieTerm(s, W, 0.5);
-            } else {
-                parts[b] = comp.compare(m_cc, dup, shifted, SignFunc, Cfg);
-            }
-            ph.mark("  rank batch: compare");
-        });
-        m_cc->JoinLanes();
-        split.gatherParts(m_cc, parts);
-        for (int b = 0; b < L.B; ++b) m_cc->EvalAddInPlace(rank, parts[b]);
-        ph.mark("rank: batches (vecRotsOpt+compare)");
-        // sum the P partitions (period N inside S slots)
-        for (int s = L.S / 2; s >= N; s /= 2) m_cc->EvalAddInPlace(rank, rot.rotate(rank, s));
-        ph.mark("rank: folds");
-        rank->SetSlots(N);
-        if (stable) {
-            // the terms' constants 1/2 + w: r over d != 0 and 1/2 from the self
-            // slots, less the self comparison below
-            const double self = 0.5 - (offsetSelf ? 1.0 : 0.5);
-            const Plaintext& base = maskMemo({12, offsetSelf ? 1 : 0, 0, (int)rank->GetLevel(), N}, [&](auto& v) {
-                std::vector<double> c(N);
-                for (int r = 0; r < N; ++r) c[r] = r + self;
-                v.push_back(m_cc->MakeCKKSPackedPlaintext(c, 1, rank->GetLevel(), nullptr, N));
-            })[0];
-            return m_cc->EvalAdd(rank, base);
-        }
-        // remove the self comparison: step(selfOffset) = 1 (reference: step(0) = 1/2)
-        return m_cc->EvalSub(rank, offsetSelf ? 1.0 : 0.5);
-    }
-
     // The lexicographic stable rank by m = keys.size() keys (1 <= m <=
     // SFHE_LEX_KEYS), key i descending where descending[i]: the number of j
     // before r in (key_1, ..., key_m, input index) order.  In
@@ -578,13 +668,13 @@ class DirectSort : public SortBase<N> {
     // term, and so on down to the index.  Per batch: the m signs, the m tie
     // terms (EvalTieTerm), q_i = s_i^2 for i < m in one EvalMultMany, then the
     // Horner steps from the last key inwards (EvalLexStep, one level each):
-    // m - 1 levels below constructRankStable.  A descending key swaps the
-    // operands of its difference.  The self offset goes on the first key's
-    // difference only (+kSelfOffset whatever its direction), so s_1 = 1 and
-    // e_1 ~ 0 in the self slots and the constants are constructRankStable's.
-    // The masks, tie weights and base constants are that method's memo
-    // entries.  Precondition per key: two values are equal or at least the
-    // sign configuration's resolution apart.
+    // m - 1 levels below constructRankStable, whose rank is the case m = 1 (no
+    // product, no Horner step).  A descending key swaps the operands of its
+    // difference.  The self offset goes on the first key's difference only
+    // (+kSelfOffset whatever its direction), so s_1 = 1 and e_1 ~ 0 in the self
+    // slots and the constants (rankBasePlain) do not depend on m.
+    // Precondition per key: two values are equal or at least the sign
+    // configuration's resolution apart.
     Ciphertext<DCRTPoly> constructRankLex(const std::vector<Ciphertext<DCRTPoly>>& keys,
                                           const std::vector<bool>& descending, SignFunc SignFunc, SignConfig& Cfg) {
         const int m = (int)keys.size();
@@ -601,27 +691,23 @@ class DirectSort : public SortBase<N> {
             throw OpenFHEException("lexicographic rank: needs multiplicative depth " + std::to_string(need) +
                                    " (the stable rank's, and one level per key after the first); the context has " +
                                    std::to_string(m_cc->GetMultiplicativeDepth()));
-        if (m == 1 && !descending[0]) return constructRankMode(keys[0], SignFunc, Cfg, true);
+        return lexRank(keys, descending, SignFunc, Cfg);
+    }
+
+    // constructRankLex's computation, after its checks
+    Ciphertext<DCRTPoly> lexRank(const std::vector<Ciphertext<DCRTPoly>>& keys, const std::vector<bool>& descending,
+                                 SignFunc SignFunc, SignConfig& Cfg) {
+        const int m = (int)keys.size();
         const sfhe::RankLayout L(N, max_batch);
         sfhe::PhaseTimer ph(m_cc);
-        std::vector<int> amounts(L.npRank);
-        for (int i = 0; i < L.npRank; ++i) amounts[i] = i;
         std::vector<std::vector<Ciphertext<DCRTPoly>>> pre(m);
-        for (int k = 0; k < m; ++k) {
-            pre[k] = rot.rotateMany(keys[k], amounts);
-            for (auto& p : pre[k]) p->SetSlots(L.S);
-        }
+        for (int k = 0; k < m; ++k) pre[k] = rankBabyRotations(keys[k], L);
         ph.mark("lex rank: baby rotations");
-
         auto rank = this->getZero()->Clone();
         rank->SetSlots(L.S);
         const bool offsetSelf = sfhe::selfOffset();
         std::vector<Ciphertext<DCRTPoly>> parts(L.B);
-        const sfhe::BatchSplit split(m_cc, L.B);
-        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
-        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());
-        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
-            const int b = split.mine[i];
+        const auto split = runBatches(L.B, [&](int b) {
             std::vector<Ciphertext<DCRTPoly>> s(m), v(m);
             for (int k = 0; k < m; ++k) {
                 // minuend - subtrahend: x_r - x_j ascending, x_j - x_r descending
@@ -630,44 +716,26 @@ class DirectSort : public SortBase<N> {
                 dup->SetSlots(L.S);
                 auto minuend = descending[k] ? shifted : dup;
                 const auto& subtrahend = descending[k] ? dup : shifted;
-                if (k == 0 && b == 0 && offsetSelf) {
-                    const Plaintext& off = maskMemo({7, 0, 0, (int)dup->GetLevel(), L.S}, [&](auto& mv) {
-                        std::vector<double> o(L.S, 0.0);
-                        std::fill(o.begin(), o.begin() + N, sfhe::kSelfOffset);
-                        mv.push_back(m_cc->MakeCKKSPackedPlaintext(o, 1, dup->GetLevel(), nullptr, L.S));
-                    })[0];
-                    minuend = m_cc->EvalAdd(minuend, off);
-                }
+                if (k == 0 && b == 0 && offsetSelf)
+                    minuend = m_cc->EvalAdd(minuend, selfOffsetPlain(dup->GetLevel(), L.S));
                 s[k] = sign(m_cc->EvalSub(minuend, subtrahend), m_cc, SignFunc, Cfg);
             }
             ph.mark("  lex rank batch: vecRotsOpt + signs");
-            const Plaintext& W = maskMemo({11, b, 0, (int)s[0]->GetLevel(), L.S}, [&](auto& mv) {
-                mv.push_back(m_cc->MakeCKKSPackedPlaintext(generateTieWeights(L.S, L.P, b), 1, s[0]->GetLevel(),
-                                                           nullptr, L.S));
-            })[0];
+            const Plaintext& W = tieWeightsPlain(b, s[0]->GetLevel(), L);
             for (int k = 0; k < m; ++k) v[k] = m_cc->EvalTieTerm(s[k], W, 0.5);
-            const std::vector<Ciphertext<DCRTPoly>> head(s.begin(), s.end() - 1);
-            const auto q = m_cc->EvalMultMany(head, head);
             auto u = v[m - 1];
-            for (int k = m - 2; k >= 0; --k) u = m_cc->EvalLexStep(v[k], q[k], u);
+            if (m > 1) {
+                const std::vector<Ciphertext<DCRTPoly>> head(s.begin(), s.end() - 1);
+                const auto q = m_cc->EvalMultMany(head, head);
+                for (int k = m - 2; k >= 0; --k) u = m_cc->EvalLexStep(v[k], q[k], u);
+            }
             parts[b] = u;
             ph.mark("  lex rank batch: tie terms + Horner steps");
         });
-        m_cc->JoinLanes();
         split.gatherParts(m_cc, parts);
-        for (int b = 0; b < L.B; ++b) m_cc->EvalAddInPlace(rank, parts[b]);
-        ph.mark("lex rank: batches");
-        for (int sft = L.S / 2; sft >= N; sft /= 2) m_cc->EvalAddInPlace(rank, rot.rotate(rank, sft));
-        ph.mark("lex rank: folds");
-        rank->SetSlots(N);
-        // the terms' constants 1/2 + w, less the self comparison (constructRankMode)
-        const double self = 0.5 - (offsetSelf ? 1.0 : 0.5);
-        const Plaintext& base = maskMemo({12, offsetSelf ? 1 : 0, 0, (int)rank->GetLevel(), N}, [&](auto& mv) {
-            std::vector<double> c(N);
-            for (int r = 0; r < N; ++r) c[r] = r + self;
-            mv.push_back(m_cc->MakeCKKSPackedPlaintext(c, 1, rank->GetLevel(), nullptr, N));
-        })[0];
-        return m_cc->EvalAdd(rank, base);
+        rank = sumOverPartitions(rank, parts, L.S);
+        ph.mark("lex rank: batch sum + folds");
+        return m_cc->EvalAdd(rank, rankBasePlain(rank->GetLevel(), offsetSelf));
     }
 
     // ---- grouping by an encrypted key (COUNT(*), SUM(col), ROW_NUMBER() OVER
@@ -686,7 +754,7 @@ class DirectSort : public SortBase<N> {
         }
         return v;
     }
-    // In constructRankMode's slot layout (slot pN + r of batch b compares row r
+    // In constructRank's slot layout (slot pN + r of batch b compares row r
     // with row j = (r + d) mod N, d = bP + p), with s_b the composite sign of
     // key_r - key_j, q_b = s_b^2 ("the keys differ") and u_bc column c's value at
     // row j in the same layout:
@@ -722,24 +790,14 @@ class DirectSort : public SortBase<N> {
                                    std::to_string(m_cc->GetMultiplicativeDepth()));
         const sfhe::RankLayout L(N, max_batch);
         sfhe::PhaseTimer ph(m_cc);
-        std::vector<int> amounts(L.npRank);
-        for (int i = 0; i < L.npRank; ++i) amounts[i] = i;
-        auto pre = rot.rotateMany(keys, amounts);
-        for (auto& p : pre) p->SetSlots(L.S);
+        const auto pre = rankBabyRotations(keys, L);
         std::vector<std::vector<Ciphertext<DCRTPoly>>> preCols(C);
-        for (size_t c = 0; c < C; ++c) {
-            preCols[c] = rot.rotateMany(cols[c], amounts);
-            for (auto& p : preCols[c]) p->SetSlots(L.S);
-        }
+        for (size_t c = 0; c < C; ++c) preCols[c] = rankBabyRotations(cols[c], L);
         ph.mark("group: baby rotations");
 
         std::vector<Ciphertext<DCRTPoly>> q(L.B), mq(wantIndex ? L.B : 0);
         std::vector<std::vector<Ciphertext<DCRTPoly>>> u(C, std::vector<Ciphertext<DCRTPoly>>(L.B));
-        const sfhe::BatchSplit split(m_cc, L.B);
-        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
-        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());
-        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
-            const int b = split.mine[i];
+        const auto split = runBatches(L.B, [&](int b) {
             auto shifted = vecRotsOpt(pre, L.P, L.S, L.npRank, b);
             for (size_t c = 0; c < C; ++c) u[c][b] = vecRotsOpt(preCols[c], L.P, L.S, L.npRank, b);
             ph.mark("  group batch: vecRotsOpt");
@@ -748,15 +806,12 @@ class DirectSort : public SortBase<N> {
             auto s = sign(m_cc->EvalSub(dup, shifted), m_cc, SignFunc, Cfg);
             q[b] = m_cc->EvalMult(s, s);
             if (wantIndex) {
-                const Plaintext& M = maskMemo({15, b, 0, (int)q[b]->GetLevel(), L.S}, [&](auto& v) {
-                    v.push_back(m_cc->MakeCKKSPackedPlaintext(generateBeforeMask(L.S, L.P, b), 1, q[b]->GetLevel(),
-                                                              nullptr, L.S));
-                })[0];
+                const Plaintext& M = memoPlain(kBeforeMask, b, 0, q[b]->GetLevel(), L.S,
+                                               [&] { return generateBeforeMask(L.S, L.P, b); });
                 mq[b] = m_cc->EvalMult(q[b], M);
             }
             ph.mark("  group batch: sign + gate");
         });
-        m_cc->JoinLanes();
         split.gatherParts(m_cc, q);
         if (wantIndex) split.gatherParts(m_cc, mq);
         for (auto& col : u) split.gatherParts(m_cc, col);
@@ -764,9 +819,7 @@ class DirectSort : public SortBase<N> {
 
         auto fold = [&](Ciphertext<DCRTPoly> x) {
             x->SetSlots(L.S);
-            for (int sft = L.S / 2; sft >= N; sft /= 2) m_cc->EvalAddInPlace(x, rot.rotate(x, sft));
-            x->SetSlots(N);
-            return x;
+            return sumOverPartitions(x, {}, L.S);
         };
         auto sumOf = [&](const std::vector<Ciphertext<DCRTPoly>>& parts) {
             auto acc = parts[0]->Clone();
@@ -782,13 +835,30 @@ class DirectSort : public SortBase<N> {
         out.count = m_cc->EvalSub((double)N, fold(sumOf(q)));
         if (wantIndex) {
             auto before = fold(sumOf(mq));
-            const Plaintext& idx = maskMemo({16, 0, 0, (int)before->GetLevel(), N}, [&](auto& v) {
-                v.push_back(m_cc->MakeCKKSPackedPlaintext(generateIndexVector(), 1, before->GetLevel(), nullptr, N));
-            })[0];
-            out.index = m_cc->EvalSub(idx, before);
+            out.index = m_cc->EvalSub(indexPlain(before->GetLevel(), kGroupIndex), before);
         }
         ph.mark("group: count + index");
         return out;
+    }
+
+    // The masks of one baby/giant-step move and its giant steps' rotation amounts
+    struct GiantMasks {
+        std::vector<const std::vector<Plaintext>*> masks;  // [giant step][baby step]
+        std::vector<int> steps;
+    };
+    // blindRotationOptN's: partition np*i + j kept, rotated by its baby step j
+    GiantMasks blindRotationMasks(int num_slots, int np, uint32_t level) {
+        std::vector<std::array<int, 5>> keys;
+        GiantMasks gm;
+        for (int i = 0; i < (num_slots / N) / np; ++i) {
+            keys.push_back({kBlindMasks, 0, i, (int)level, num_slots});
+            gm.steps.push_back(i * np);
+        }
+        gm.masks = maskMemoMany(keys, np, [&](size_t i, int j) {
+            return m_cc->MakeCKKSPackedPlaintext(vectorRotate(generateMaskVectorN(num_slots, np * (int)i + j), j), 1,
+                                                 level, nullptr, num_slots);
+        });
+        return gm;
     }
 
     // Rotates partition k = np*i + j of the masked inputs left by ib*P + k
@@ -796,21 +866,36 @@ class DirectSort : public SortBase<N> {
     // rotateSum over i*np).
     Ciphertext<DCRTPoly> blindRotationOptN(const std::vector<Ciphertext<DCRTPoly>>& masked_inputs,
                                            int num_slots, int np, int ib, int num_partition) {
-        std::vector<std::array<int, 5>> keys;
-        std::vector<int> steps;
-        for (int i = 0; i < (num_slots / N) / np; ++i) {
-            keys.push_back({1, 0, i, (int)masked_inputs[0]->GetLevel(), num_slots});
-            steps.push_back(i * np);
-        }
-        const auto masks = maskMemoMany(keys, np, [&](size_t i, int j) {
-            return m_cc->MakeCKKSPackedPlaintext(vectorRotate(generateMaskVectorN(num_slots, np * (int)i + j), j), 1,
-                                                 masked_inputs[j]->GetLevel(), nullptr, num_slots);
-        });
+        const auto gm = blindRotationMasks(num_slots, np, masked_inputs[0]->GetLevel());
         std::vector<Ciphertext<DCRTPoly>> giants;
-        for (const auto* m : masks) giants.push_back(m_cc->EvalMultAddPlain(masked_inputs, *m));
+        for (const auto* m : gm.masks) giants.push_back(m_cc->EvalMultAddPlain(masked_inputs, *m));
         auto result = this->getZero()->Clone();
-        m_cc->EvalAddInPlace(result, rot.rotate(rot.rotateSum(giants, steps), ib * num_partition));
+        m_cc->EvalAddInPlace(result, rot.rotate(rot.rotateSum(giants, gm.steps), ib * num_partition));
         return result;
+    }
+    // blindRotationOptN of several columns' masked inputs [c][j]: the columns
+    // share the masks, so their giant-step sums are formed together
+    // (EvalMultAddPlainCols); each column's sums then rotate as there.
+    std::vector<Ciphertext<DCRTPoly>> blindRotationOptNCols(
+        const std::vector<std::vector<Ciphertext<DCRTPoly>>>& masked_inputs, int num_slots, int np, int ib,
+        int num_partition) {
+        const auto gm = blindRotationMasks(num_slots, np, masked_inputs[0][0]->GetLevel());
+        const auto giants = m_cc->EvalMultAddPlainCols(masked_inputs, gm.masks);
+        std::vector<Ciphertext<DCRTPoly>> results;
+        for (const auto& g : giants) {
+            auto result = this->getZero()->Clone();
+            m_cc->EvalAddInPlace(result, rot.rotate(rot.rotateSum(g, gm.steps), ib * num_partition));
+            results.push_back(result);
+        }
+        return results;
+    }
+
+    // index - rank at S slots: what both placements compare with their
+    // batches' checking vectors
+    Ciphertext<DCRTPoly> indexMinusRank(const Ciphertext<DCRTPoly>& ctx_Rank, const sfhe::RankLayout& L) {
+        auto d = m_cc->EvalSub(indexPlain(ctx_Rank->GetLevel()), ctx_Rank);
+        d->SetSlots(L.S);
+        return d;
     }
 
     Ciphertext<DCRTPoly> rotationIndexCheckN(const Ciphertext<DCRTPoly>& ctx_Rank,
@@ -818,97 +903,34 @@ class DirectSort : public SortBase<N> {
         const sfhe::RankLayout L(N, max_batch);
         sfhe::PhaseTimer ph(m_cc);
         auto output = this->getZero()->Clone();
-        Plaintext idx = maskMemo({2, 0, 0, (int)ctx_Rank->GetLevel(), N}, [&](auto& v) {
-            v.push_back(m_cc->MakeCKKSPackedPlaintext(generateIndexVector(), 1, ctx_Rank->GetLevel(), nullptr, N));
-        })[0];
-        auto indexMinusRank = m_cc->EvalSub(idx, ctx_Rank);
-        indexMinusRank->SetSlots(L.S);
+        const auto offset = indexMinusRank(ctx_Rank, L);
         input_array->SetSlots(L.S);  // reference side effect (sort_algo.h:711)
-
-        // The doubled sinc p is evaluated on y = (4z + 1)/3, its argument's
-        // range z in (-1, 1/2) mapped onto [-1, 1]: the same polynomial
-        // (re-expanded, sfhe::rebasedChebyshev), the same levels, but the
-        // hits z = 0 land at y = 1/3 instead of an extremum of every giant
-        // step T_{2^i}, which cuts the CKKS noise of the placement ~2^8-fold
-        // (DESIGN.md §2).  SFHE_SINC_REBASE=0 evaluates p(z) as the reference.
-        const bool rebase = sfhe::sincRebase();
-        const auto& sincCoeffs = rebase ? sfhe::rebasedChebyshev(selectDoubledSincCoefficients<N>(), -1.0, 0.5)
-                                        : selectDoubledSincCoefficients<N>();
-        const double zmul = rebase ? 4.0 / 3.0 : 1.0, zadd = rebase ? 1.0 / 3.0 : 0.0;
+        const sfhe::SincIndicator ind(N);
         std::vector<Ciphertext<DCRTPoly>> parts(L.B);
-        const sfhe::BatchSplit split(m_cc, L.B);
-        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
-        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());  // (one batch: no region, the PS may open its own)
-        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
-            const int b = split.mine[i];
-            Plaintext chk = maskMemo({3, b, 0, (int)indexMinusRank->GetLevel(), L.S}, [&](auto& v) {
-                v.push_back(m_cc->MakeCKKSPackedPlaintext(generateCheckingVectorN(L.S, b * L.P), 1,
-                                                          indexMinusRank->GetLevel(), nullptr, L.S));
-            })[0];
+        const auto split = runBatches(L.B, [&](int b) {
             // (r - rank_r - c) / 2N  in (-1, 1/2)
-            auto z = m_cc->EvalMult(m_cc->EvalSub(indexMinusRank, chk), zmul / N / 2);
-            if (rebase) z = m_cc->EvalAdd(z, zadd);
-            ph.mark("  place batch: z");
-            auto hit = m_cc->EvalChebyshevSeriesPS(z, sincCoeffs, -1, 1);
-            // the rebased series may be shorter (tiny tail terms dropped) and so
-            // shallower: consume exactly the reference's PS depth (level tables)
-            const uint32_t psLevel = z->GetLevel() + lbcrypto::ChebyshevPSDepth(
-                (uint32_t)selectDoubledSincCoefficients<N>().size() - 1);
-            if (hit->GetLevel() < psLevel) hit = m_cc->AdjustLevel(hit, psLevel);
-            ph.mark("  place batch: sinc PS");
+            auto hit = ind.hit(m_cc, m_cc->EvalSub(offset, checkingPlain(b, offset->GetLevel(), L)), ph);
             auto masked = m_cc->EvalMult(hit, input_array);
-            std::vector<int> amounts(L.npPlace);
-            for (int i = 0; i < L.npPlace; ++i) amounts[i] = i;
-            auto maskedRot = rot.rotateMany(masked, amounts);
+            auto maskedRot = rot.rotateMany(masked, babySteps(L.npPlace));
             ph.mark("  place batch: mask + baby rotations");
             parts[b] = blindRotationOptN(maskedRot, L.S, L.npPlace, b, L.P);
             ph.mark("  place batch: blind rotation");
         });
-        m_cc->JoinLanes();
         split.gatherParts(m_cc, parts);
-        for (int b = 0; b < L.B; ++b) m_cc->EvalAddInPlace(output, parts[b]);
-        ph.mark("place: batches (sinc PS+mask+blind rotation)");
-        for (int s = L.S / 2; s >= N; s /= 2) m_cc->EvalAddInPlace(output, rot.rotate(output, s));
-        ph.mark("place: folds");
-        output->SetSlots(N);
+        output = sumOverPartitions(output, parts, L.S);
+        ph.mark("place: batch sum + folds");
         return output;
-    }
-
-    // blindRotationOptN of several columns' masked inputs [c][j]: the columns
-    // share the masks, so their giant-step sums are formed together
-    // (EvalMultAddPlainCols); each column's sums then rotate as there.
-    std::vector<Ciphertext<DCRTPoly>> blindRotationOptNCols(
-        const std::vector<std::vector<Ciphertext<DCRTPoly>>>& masked_inputs, int num_slots, int np, int ib,
-        int num_partition) {
-        std::vector<std::array<int, 5>> keys;
-        std::vector<int> steps;
-        for (int i = 0; i < (num_slots / N) / np; ++i) {
-            keys.push_back({1, 0, i, (int)masked_inputs[0][0]->GetLevel(), num_slots});
-            steps.push_back(i * np);
-        }
-        const auto masks = maskMemoMany(keys, np, [&](size_t i, int j) {
-            return m_cc->MakeCKKSPackedPlaintext(vectorRotate(generateMaskVectorN(num_slots, np * (int)i + j), j), 1,
-                                                 masked_inputs[0][j]->GetLevel(), nullptr, num_slots);
-        });
-        const auto giants = m_cc->EvalMultAddPlainCols(masked_inputs, masks);
-        std::vector<Ciphertext<DCRTPoly>> results;
-        for (const auto& g : giants) {
-            auto result = this->getZero()->Clone();
-            m_cc->EvalAddInPlace(result, rot.rotate(rot.rotateSum(g, steps), ib * num_partition));
-            results.push_back(result);
-        }
-        return results;
     }
 
     // The placement of several columns by ONE rank (records: a key and its
     // payload columns).  The indicator `hit` depends on the
-    // rank alone: per batch z, the doubled-sinc PS and its level adjustment
-    // run once, exactly as in rotationIndexCheckN, and only the linear tail
-    // (hit (.) column, baby rotations, blind rotation, batch sum, folds) runs
-    // per column.  Column c of the result holds the residues of
-    // rotationIndexCheckN(ctx_Rank, cols[c]): the arithmetic is exact on
-    // canonical residues, so sharing `hit` changes none of them.  Every
-    // column is left at S slots, as rotationIndexCheckN leaves its input.
+    // rank alone: per batch it is evaluated once, exactly as in
+    // rotationIndexCheckN, and only the linear tail (hit (.) column, baby
+    // rotations, blind rotation, batch sum, folds) runs per column.  Column c
+    // of the result holds the residues of rotationIndexCheckN(ctx_Rank,
+    // cols[c]): the arithmetic is exact on canonical residues, so sharing
+    // `hit` changes none of them.  Every column is left at S slots, as
+    // rotationIndexCheckN leaves its input.
     std::vector<Ciphertext<DCRTPoly>> placeMany(const Ciphertext<DCRTPoly>& ctx_Rank,
                                                 const std::vector<Ciphertext<DCRTPoly>>& cols) {
         if (cols.empty()) throw OpenFHEException("placeMany: no columns");
@@ -918,53 +940,25 @@ class DirectSort : public SortBase<N> {
         const sfhe::RankLayout L(N, max_batch);
         sfhe::PhaseTimer ph(m_cc);
         const size_t C = cols.size();
-        Plaintext idx = maskMemo({2, 0, 0, (int)ctx_Rank->GetLevel(), N}, [&](auto& v) {
-            v.push_back(m_cc->MakeCKKSPackedPlaintext(generateIndexVector(), 1, ctx_Rank->GetLevel(), nullptr, N));
-        })[0];
-        auto indexMinusRank = m_cc->EvalSub(idx, ctx_Rank);
-        indexMinusRank->SetSlots(L.S);
+        const auto offset = indexMinusRank(ctx_Rank, L);
         for (const auto& c : cols) c->SetSlots(L.S);  // (rotationIndexCheckN's side effect on its input)
-        const bool rebase = sfhe::sincRebase();
-        const auto& sincCoeffs = rebase ? sfhe::rebasedChebyshev(selectDoubledSincCoefficients<N>(), -1.0, 0.5)
-                                        : selectDoubledSincCoefficients<N>();
-        const double zmul = rebase ? 4.0 / 3.0 : 1.0, zadd = rebase ? 1.0 / 3.0 : 0.0;
+        const sfhe::SincIndicator ind(N);
         std::vector<std::vector<Ciphertext<DCRTPoly>>> parts(C, std::vector<Ciphertext<DCRTPoly>>(L.B));
-        const sfhe::BatchSplit split(m_cc, L.B);
-        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
-        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());
-        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
-            const int b = split.mine[i];
-            Plaintext chk = maskMemo({3, b, 0, (int)indexMinusRank->GetLevel(), L.S}, [&](auto& v) {
-                v.push_back(m_cc->MakeCKKSPackedPlaintext(generateCheckingVectorN(L.S, b * L.P), 1,
-                                                          indexMinusRank->GetLevel(), nullptr, L.S));
-            })[0];
-            auto z = m_cc->EvalMult(m_cc->EvalSub(indexMinusRank, chk), zmul / N / 2);
-            if (rebase) z = m_cc->EvalAdd(z, zadd);
-            ph.mark("  place batch: z");
-            auto hit = m_cc->EvalChebyshevSeriesPS(z, sincCoeffs, -1, 1);
-            const uint32_t psLevel = z->GetLevel() + lbcrypto::ChebyshevPSDepth(
-                (uint32_t)selectDoubledSincCoefficients<N>().size() - 1);
-            if (hit->GetLevel() < psLevel) hit = m_cc->AdjustLevel(hit, psLevel);
-            ph.mark("  place batch: sinc PS (shared)");
-            std::vector<int> amounts(L.npPlace);
-            for (int k = 0; k < L.npPlace; ++k) amounts[k] = k;
+        const auto split = runBatches(L.B, [&](int b) {
+            auto hit = ind.hit(m_cc, m_cc->EvalSub(offset, checkingPlain(b, offset->GetLevel(), L)), ph);
             std::vector<std::vector<Ciphertext<DCRTPoly>>> maskedRot(C);
-            for (size_t c = 0; c < C; ++c) maskedRot[c] = rot.rotateMany(m_cc->EvalMult(hit, cols[c]), amounts);
+            for (size_t c = 0; c < C; ++c)
+                maskedRot[c] = rot.rotateMany(m_cc->EvalMult(hit, cols[c]), babySteps(L.npPlace));
             ph.mark("  place batch: masks + baby rotations");
             auto placed = blindRotationOptNCols(maskedRot, L.S, L.npPlace, b, L.P);
             for (size_t c = 0; c < C; ++c) parts[c][b] = placed[c];
             ph.mark("  place batch: blind rotations");
         });
-        m_cc->JoinLanes();
         m_cc->NotePlacement(split.mine.size(), C);
         std::vector<Ciphertext<DCRTPoly>> outputs(C);
         for (size_t c = 0; c < C; ++c) {
             split.gatherParts(m_cc, parts[c]);
-            auto output = this->getZero()->Clone();
-            for (int b = 0; b < L.B; ++b) m_cc->EvalAddInPlace(output, parts[c][b]);
-            for (int s = L.S / 2; s >= N; s /= 2) m_cc->EvalAddInPlace(output, rot.rotate(output, s));
-            output->SetSlots(N);
-            outputs[c] = output;
+            outputs[c] = sumOverPartitions(this->getZero()->Clone(), parts[c], L.S);
         }
         ph.mark("place: batch sums + folds");
         return outputs;
@@ -1012,7 +1006,8 @@ class DirectSort : public SortBase<N> {
     }
 
     // the checks every selection runs first: the target list, and the depth a rank at this level needs
-    int selectCheck(const Ciphertext<DCRTPoly>& ctx_Rank, const std::vector<int>& targets) {
+    void selectCheck(const Ciphertext<DCRTPoly>& ctx_Rank, const std::vector<int>& targets,
+                     const sfhe::SincIndicator& ind) {
         const int K = (int)targets.size();
         if (K < 1 || K > N) throw std::invalid_argument("select: the target count must be in [1, N]");
         {
@@ -1024,94 +1019,93 @@ class DirectSort : public SortBase<N> {
                 seen[t] = 1;
             }
         }
-        const int ps = (int)lbcrypto::ChebyshevPSDepth((uint32_t)selectDoubledSincCoefficients<N>().size() - 1);
-        const int need = (int)ctx_Rank->GetLevel() + 1 + ps + 1 + 1;
+        const int need = (int)ctx_Rank->GetLevel() + 1 + (int)ind.psDepth + 1 + 1;
         if ((int)m_cc->GetMultiplicativeDepth() < need)
             throw OpenFHEException("select: needs multiplicative depth " + std::to_string(need) +
                                    " from a rank at level " + std::to_string(ctx_Rank->GetLevel()) +
                                    "; the context has " + std::to_string(m_cc->GetMultiplicativeDepth()));
-        return ps;
     }
+
+    // The target-major layout of a selection of K = targets.size() ranks, and
+    // the target list's memo id.
+    struct SelectLayout {
+        int K, Psel, S, B, np, tid;
+    };
+    SelectLayout selectLayout(const std::vector<int>& targets) {
+        const sfhe::RankLayout L(N, max_batch);
+        SelectLayout sel;
+        sel.K = (int)targets.size();
+        sel.Psel = 1;
+        while (sel.Psel < sel.K && sel.Psel < L.P) sel.Psel *= 2;
+        sel.S = N * sel.Psel;
+        sel.B = (sel.K + sel.Psel - 1) / sel.Psel;
+        sel.np = 1 << (sfhe::ilog2(sel.Psel) / 2);
+        sel.tid = targetListId(targets);
+        return sel;
+    }
+    // T[pN + r] = targets[b Psel + p] (a padded partition repeats the batch's first target)
+    const Plaintext& targetPlain(const SelectLayout& sel, const std::vector<int>& targets, int b, uint32_t level) {
+        return memoPlain(kTargets, b, sel.tid, level, sel.S, [&] {
+            std::vector<double> T(sel.S);
+            for (int p = 0; p < sel.Psel; ++p) {
+                const int k = b * sel.Psel + p;
+                std::fill(T.begin() + (size_t)p * N, T.begin() + (size_t)(p + 1) * N,
+                          (double)targets[k < sel.K ? k : b * sel.Psel]);
+            }
+            return T;
+        });
+    }
+    // The move of batch b: slot pN of the real targets kept, inside baby steps
+    // j and giant steps np g (p' = Psel - 1 - p = np g + j); base_b follows.
+    GiantMasks moveMasks(const SelectLayout& sel, int b, uint32_t level) {
+        std::vector<std::array<int, 5>> keys;
+        GiantMasks gm;
+        for (int g = 0; g < sel.Psel / sel.np; ++g) {
+            keys.push_back({kMoveMasks, sel.tid, b * 1024 + g, (int)level, sel.S});
+            gm.steps.push_back(g * sel.np);
+        }
+        gm.masks = maskMemoMany(keys, sel.np, [&](size_t g, int j) {
+            std::vector<double> m(sel.S, 0.0);
+            const int p = sel.Psel - 1 - (sel.np * (int)g + j);
+            if (b * sel.Psel + p < sel.K) m[(size_t)p * N] = 1.0;
+            return m_cc->MakeCKKSPackedPlaintext(vectorRotate(m, j), 1, level, nullptr, sel.S);
+        });
+        return gm;
+    }
+    int moveBase(const SelectLayout& sel, int b) const { return (N + 1 - (b + 1) * sel.Psel) % sel.S; }
 
     Ciphertext<DCRTPoly> selectRanks(const Ciphertext<DCRTPoly>& ctx_Rank, const Ciphertext<DCRTPoly>& input_array,
                                      const std::vector<int>& targets) {
-        const int ps = selectCheck(ctx_Rank, targets);
-        const int K = (int)targets.size();
-        const sfhe::RankLayout L(N, max_batch);
+        const sfhe::SincIndicator ind(N);
+        selectCheck(ctx_Rank, targets, ind);
+        const auto sel = selectLayout(targets);
         sfhe::PhaseTimer ph(m_cc);
-        int Psel = 1;
-        while (Psel < K && Psel < L.P) Psel *= 2;
-        const int S = N * Psel, Bsel = (K + Psel - 1) / Psel;
-        const int np = 1 << (sfhe::ilog2(Psel) / 2);
-        const int tid = targetListId(targets);
         auto rankS = ctx_Rank->Clone();
-        rankS->SetSlots(S);
+        rankS->SetSlots(sel.S);
         auto input = input_array->Clone();
-        input->SetSlots(S);
-        const bool rebase = sfhe::sincRebase();
-        const auto& sincCoeffs = rebase ? sfhe::rebasedChebyshev(selectDoubledSincCoefficients<N>(), -1.0, 0.5)
-                                        : selectDoubledSincCoefficients<N>();
-        const double zmul = rebase ? 4.0 / 3.0 : 1.0, zadd = rebase ? 1.0 / 3.0 : 0.0;
-        std::vector<Ciphertext<DCRTPoly>> parts(Bsel);
-        const sfhe::BatchSplit split(m_cc, Bsel);
-        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
-        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());
-        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
-            const int b = split.mine[i];
-            // T[pN + r] = targets[b Psel + p] (a padded partition repeats the batch's first target)
-            Plaintext tgt = maskMemo({13, b, tid, (int)rankS->GetLevel(), S}, [&](auto& v) {
-                std::vector<double> T(S);
-                for (int p = 0; p < Psel; ++p) {
-                    const int k = b * Psel + p;
-                    std::fill(T.begin() + (size_t)p * N, T.begin() + (size_t)(p + 1) * N,
-                              (double)targets[k < K ? k : b * Psel]);
-                }
-                v.push_back(m_cc->MakeCKKSPackedPlaintext(T, 1, rankS->GetLevel(), nullptr, S));
-            })[0];
+        input->SetSlots(sel.S);
+        std::vector<Ciphertext<DCRTPoly>> parts(sel.B);
+        const auto split = runBatches(sel.B, [&](int b) {
             // (t - rank_r) / 2N  in (-1/2, 1/2)
-            auto z = m_cc->EvalMult(m_cc->EvalSub(tgt, rankS), zmul / N / 2);
-            if (rebase) z = m_cc->EvalAdd(z, zadd);
-            ph.mark("  select batch: z");
-            auto hit = m_cc->EvalChebyshevSeriesPS(z, sincCoeffs, -1, 1);
-            const uint32_t psLevel = z->GetLevel() + (uint32_t)ps;
-            if (hit->GetLevel() < psLevel) hit = m_cc->AdjustLevel(hit, psLevel);
-            ph.mark("  select batch: sinc PS");
+            auto hit = ind.hit(m_cc, m_cc->EvalSub(targetPlain(sel, targets, b, rankS->GetLevel()), rankS), ph);
             auto summed = foldPartitions(m_cc->EvalMult(hit, input));
             ph.mark("  select batch: mask + in-partition folds");
-            // the move: baby steps j, giant steps np i, then base_b
-            std::vector<int> amounts(np);
-            for (int j = 0; j < np; ++j) amounts[j] = j;
-            auto pre = rot.rotateMany(summed, amounts);
-            std::vector<std::array<int, 5>> keys;
-            std::vector<int> steps;
-            for (int g = 0; g < Psel / np; ++g) {
-                keys.push_back({14, tid, b * 1024 + g, (int)pre[0]->GetLevel(), S});
-                steps.push_back(g * np);
-            }
-            const auto masks = maskMemoMany(keys, np, [&](size_t g, int j) {
-                std::vector<double> m(S, 0.0);
-                const int p = Psel - 1 - (np * (int)g + j);
-                if (b * Psel + p < K) m[(size_t)p * N] = 1.0;
-                return m_cc->MakeCKKSPackedPlaintext(vectorRotate(m, j), 1, pre[j]->GetLevel(), nullptr, S);
-            });
+            auto pre = rot.rotateMany(summed, babySteps(sel.np));
+            const auto gm = moveMasks(sel, b, pre[0]->GetLevel());
             std::vector<Ciphertext<DCRTPoly>> giants;
-            for (const auto* m : masks) {
+            for (const auto* m : gm.masks) {
                 giants.push_back(m_cc->EvalMultAddPlain(pre, *m));
-                giants.back()->SetSlots(S);
+                giants.back()->SetSlots(sel.S);
             }
-            const int base = (N + 1 - (b + 1) * Psel) % S;
-            parts[b] = rot.rotate(rot.rotateSum(giants, steps), base);
+            parts[b] = rot.rotate(rot.rotateSum(giants, gm.steps), moveBase(sel, b));
             ph.mark("  select batch: move");
         });
-        m_cc->JoinLanes();
         m_cc->NoteSelection(split.mine.size());
         split.gatherParts(m_cc, parts);
         auto output = this->getZero()->Clone();
-        output->SetSlots(S);
-        for (int b = 0; b < Bsel; ++b) m_cc->EvalAddInPlace(output, parts[b]);
-        for (int s = S / 2; s >= N; s /= 2) m_cc->EvalAddInPlace(output, rot.rotate(output, s));
+        output->SetSlots(sel.S);
+        output = sumOverPartitions(output, parts, sel.S);
         ph.mark("select: batch sum + folds");
-        output->SetSlots(N);
         return output;
     }
 
@@ -1132,13 +1126,12 @@ class DirectSort : public SortBase<N> {
 
     // The selection of several columns by ONE rank (ORDER BY key LIMIT k over
     // rows).  As in placeMany the indicator depends on the rank
-    // and the target list alone: per batch tgt, z, the doubled-sinc PS and its
-    // level adjustment run once, exactly as in selectRanks (same memo tags,
-    // same target-list id, no masks of its own), and the linear tail runs per
-    // column -- the in-partition folds of all columns by EvalRotateFoldMany,
-    // the move's giant-step sums by EvalMultAddPlainCols (shared masks).
-    // Column c of the result holds the residues of selectRanks(ctx_Rank,
-    // cols[c], targets).
+    // and the target list alone: per batch it is evaluated once, exactly as in
+    // selectRanks (the same target plaintexts and move masks, no memo entries
+    // of its own), and the linear tail runs per column -- the in-partition
+    // folds of all columns by EvalRotateFoldMany, the move's giant-step sums by
+    // EvalMultAddPlainCols (shared masks).  Column c of the result holds the
+    // residues of selectRanks(ctx_Rank, cols[c], targets).
     std::vector<Ciphertext<DCRTPoly>> selectRanksMany(const Ciphertext<DCRTPoly>& ctx_Rank,
                                                       const std::vector<Ciphertext<DCRTPoly>>& cols,
                                                       const std::vector<int>& targets) {
@@ -1146,89 +1139,43 @@ class DirectSort : public SortBase<N> {
         for (const auto& c : cols)
             if (c->GetLevel() != cols[0]->GetLevel())
                 throw OpenFHEException("selectRanksMany: the columns must be at one level");
-        const int ps = selectCheck(ctx_Rank, targets);
-        const int K = (int)targets.size();
+        const sfhe::SincIndicator ind(N);
+        selectCheck(ctx_Rank, targets, ind);
+        const auto sel = selectLayout(targets);
         const size_t C = cols.size();
-        const sfhe::RankLayout L(N, max_batch);
         sfhe::PhaseTimer ph(m_cc);
-        int Psel = 1;
-        while (Psel < K && Psel < L.P) Psel *= 2;
-        const int S = N * Psel, Bsel = (K + Psel - 1) / Psel;
-        const int np = 1 << (sfhe::ilog2(Psel) / 2);
-        const int tid = targetListId(targets);
         auto rankS = ctx_Rank->Clone();
-        rankS->SetSlots(S);
+        rankS->SetSlots(sel.S);
         std::vector<Ciphertext<DCRTPoly>> inputs(C);
         for (size_t c = 0; c < C; ++c) {
             inputs[c] = cols[c]->Clone();
-            inputs[c]->SetSlots(S);
+            inputs[c]->SetSlots(sel.S);
         }
-        const bool rebase = sfhe::sincRebase();
-        const auto& sincCoeffs = rebase ? sfhe::rebasedChebyshev(selectDoubledSincCoefficients<N>(), -1.0, 0.5)
-                                        : selectDoubledSincCoefficients<N>();
-        const double zmul = rebase ? 4.0 / 3.0 : 1.0, zadd = rebase ? 1.0 / 3.0 : 0.0;
-        std::vector<std::vector<Ciphertext<DCRTPoly>>> parts(C, std::vector<Ciphertext<DCRTPoly>>(Bsel));
-        const sfhe::BatchSplit split(m_cc, Bsel);
-        const int lanes = std::min((int)split.mine.size(), m_cc->LaneCount());
-        if (lanes > 1) m_cc->ForkLanes(lanes, sfhe::stackBatches());
-        sfhe::parallelLanes(m_cc, lanes, (int)split.mine.size(), [&](int i) {
-            const int b = split.mine[i];
-            Plaintext tgt = maskMemo({13, b, tid, (int)rankS->GetLevel(), S}, [&](auto& v) {
-                std::vector<double> T(S);
-                for (int p = 0; p < Psel; ++p) {
-                    const int k = b * Psel + p;
-                    std::fill(T.begin() + (size_t)p * N, T.begin() + (size_t)(p + 1) * N,
-                              (double)targets[k < K ? k : b * Psel]);
-                }
-                v.push_back(m_cc->MakeCKKSPackedPlaintext(T, 1, rankS->GetLevel(), nullptr, S));
-            })[0];
-            auto z = m_cc->EvalMult(m_cc->EvalSub(tgt, rankS), zmul / N / 2);
-            if (rebase) z = m_cc->EvalAdd(z, zadd);
-            ph.mark("  select batch: z");
-            auto hit = m_cc->EvalChebyshevSeriesPS(z, sincCoeffs, -1, 1);
-            const uint32_t psLevel = z->GetLevel() + (uint32_t)ps;
-            if (hit->GetLevel() < psLevel) hit = m_cc->AdjustLevel(hit, psLevel);
-            ph.mark("  select batch: sinc PS (shared)");
+        std::vector<std::vector<Ciphertext<DCRTPoly>>> parts(C, std::vector<Ciphertext<DCRTPoly>>(sel.B));
+        const auto split = runBatches(sel.B, [&](int b) {
+            auto hit = ind.hit(m_cc, m_cc->EvalSub(targetPlain(sel, targets, b, rankS->GetLevel()), rankS), ph);
             std::vector<Ciphertext<DCRTPoly>> masked(C);
             for (size_t c = 0; c < C; ++c) masked[c] = m_cc->EvalMult(hit, inputs[c]);
             const auto summed = foldPartitionsMany(masked);
             ph.mark("  select batch: masks + in-partition folds");
-            std::vector<int> amounts(np);
-            for (int j = 0; j < np; ++j) amounts[j] = j;
             std::vector<std::vector<Ciphertext<DCRTPoly>>> pre(C);
-            for (size_t c = 0; c < C; ++c) pre[c] = rot.rotateMany(summed[c], amounts);
-            std::vector<std::array<int, 5>> keys;
-            std::vector<int> steps;
-            for (int g = 0; g < Psel / np; ++g) {
-                keys.push_back({14, tid, b * 1024 + g, (int)pre[0][0]->GetLevel(), S});
-                steps.push_back(g * np);
-            }
-            const auto masks = maskMemoMany(keys, np, [&](size_t g, int j) {
-                std::vector<double> m(S, 0.0);
-                const int p = Psel - 1 - (np * (int)g + j);
-                if (b * Psel + p < K) m[(size_t)p * N] = 1.0;
-                return m_cc->MakeCKKSPackedPlaintext(vectorRotate(m, j), 1, pre[0][j]->GetLevel(), nullptr, S);
-            });
-            const auto giants = m_cc->EvalMultAddPlainCols(pre, masks);
-            const int base = (N + 1 - (b + 1) * Psel) % S;
+            for (size_t c = 0; c < C; ++c) pre[c] = rot.rotateMany(summed[c], babySteps(sel.np));
+            const auto gm = moveMasks(sel, b, pre[0][0]->GetLevel());
+            const auto giants = m_cc->EvalMultAddPlainCols(pre, gm.masks);
             for (size_t c = 0; c < C; ++c) {
-                for (const auto& gct : giants[c]) gct->SetSlots(S);
-                parts[c][b] = rot.rotate(rot.rotateSum(giants[c], steps), base);
+                for (const auto& gct : giants[c]) gct->SetSlots(sel.S);
+                parts[c][b] = rot.rotate(rot.rotateSum(giants[c], gm.steps), moveBase(sel, b));
             }
             ph.mark("  select batch: moves");
         });
-        m_cc->JoinLanes();
         m_cc->NoteSelection(split.mine.size());
         m_cc->NoteSelectionColumns(C);
         std::vector<Ciphertext<DCRTPoly>> outputs(C);
         for (size_t c = 0; c < C; ++c) {
             split.gatherParts(m_cc, parts[c]);
             auto output = this->getZero()->Clone();
-            output->SetSlots(S);
-            for (int b = 0; b < Bsel; ++b) m_cc->EvalAddInPlace(output, parts[c][b]);
-            for (int sft = S / 2; sft >= N; sft /= 2) m_cc->EvalAddInPlace(output, rot.rotate(output, sft));
-            output->SetSlots(N);
-            outputs[c] = output;
+            output->SetSlots(sel.S);
+            outputs[c] = sumOverPartitions(output, parts[c], sel.S);
         }
         ph.mark("select: batch sums + folds");
         return outputs;
@@ -1314,7 +1261,7 @@ class DirectSort : public SortBase<N> {
         for (size_t i = 0; i < path.size(); ++i, step >>= 1)
             c = m_cc->EvalAdd(c, rot.rotate(c, path[i] ? -(int)step : (int)step));
         if (maskOutput) {
-            const Plaintext& pmsk = maskMemo({4, (int)matrixSize, (int)columnIndex, (int)c->GetLevel(), 0},
+            const Plaintext& pmsk = maskMemo({kColumnMask, (int)matrixSize, (int)columnIndex, (int)c->GetLevel(), 0},
                                              [&](auto& v) {
                                                  std::vector<double> msk(matrixSize * matrixSize, 0.0);
                                                  for (size_t i = 0; i < matrixSize; ++i)
@@ -1338,7 +1285,7 @@ class DirectSort : public SortBase<N> {
         for (size_t i = 0; i < path.size(); ++i, step >>= 1)
             c = m_cc->EvalAdd(c, rot.rotate(c, path[i] ? -(int)step : (int)step));
         if (maskOutput) {
-            const Plaintext& pmsk = maskMemo({5, (int)matrixSize, (int)rowIndex, (int)c->GetLevel(), 0},
+            const Plaintext& pmsk = maskMemo({kRowMask, (int)matrixSize, (int)rowIndex, (int)c->GetLevel(), 0},
                                              [&](auto& v) {
                                                  std::vector<double> msk(matrixSize * matrixSize, 0.0);
                                                  for (size_t i = 0; i < matrixSize; ++i)
@@ -1411,7 +1358,7 @@ class DirectSort : public SortBase<N> {
         // dg_i = (log2 N + 1) / 2 truncated (reference :1126-1127)
         const uint32_t dg_i = (uint32_t)((std::log2((double)N) + 1) / 2);
         const uint32_t df_i = 2;
-        return matrixPlacement(ctx_Rank, input_array, 1.0, 6, [&](const Ciphertext<DCRTPoly>& c) {
+        return matrixPlacement(ctx_Rank, input_array, 1.0, kHybrid1Sub, [&](const Ciphertext<DCRTPoly>& c) {
             return mehp24::utils::indicatorAdv(c, (double)N, dg_i, df_i);
         });
     }
@@ -1431,7 +1378,7 @@ class DirectSort : public SortBase<N> {
         (void)sk;
         ctx_Rank->SetSlots(N > 256 ? (uint32_t)max_batch : (uint32_t)(N * N));
         auto r = m_cc->EvalMult(ctx_Rank, 1.0 / N);
-        return matrixPlacement(r, input_array, 1.0 / N, 8, [&](const Ciphertext<DCRTPoly>& c) {
+        return matrixPlacement(r, input_array, 1.0 / N, kHybridSub, [&](const Ciphertext<DCRTPoly>& c) {
             if (N < 256) return m_cc->EvalChebyshevSeriesPS(c, selectCoefficients<N>(), -1, 1);
             SignConfig icfg(CompositeSignConfig(3, N < 512 ? 4 : 5, 2));
             return comp.indicator(m_cc, c, 0.5 / N, SignFunc::CompositeSign, icfg);
@@ -1451,7 +1398,7 @@ class DirectSort : public SortBase<N> {
         (void)sk;
         ctx_Rank->SetSlots(N > 256 ? (uint32_t)max_batch : (uint32_t)(N * N));
         auto r = m_cc->EvalMult(ctx_Rank, 1.0 / N);
-        return matrixPlacement(r, input_array, 1.0 / N, 8, [&](const Ciphertext<DCRTPoly>& c) {
+        return matrixPlacement(r, input_array, 1.0 / N, kHybridSub, [&](const Ciphertext<DCRTPoly>& c) {
             return m_cc->EvalChebyshevSeriesPS(c, selectCoefficients<N>(), -1, 1);
         });
     }
@@ -1473,7 +1420,7 @@ class DirectSort : public SortBase<N> {
         std::vector<Ciphertext<DCRTPoly>> giants;
         std::vector<int> steps;
         for (int i = 0; i < (num_slots / N / 2) / np; ++i) {
-            auto& masks = maskMemo({9, 0, i, (int)masked_inputs[0]->GetLevel(), num_slots}, [&](auto& v) {
+            auto& masks = maskMemo({kBlindMasks2N, 0, i, (int)masked_inputs[0]->GetLevel(), num_slots}, [&](auto& v) {
                 for (int j = 0; j < np; ++j)
                     v.push_back(m_cc->MakeCKKSPackedPlaintext(vectorRotate(generateMaskVector2N(num_slots, np * i + j), j),
                                                               1, masked_inputs[j]->GetLevel(), nullptr, num_slots));
@@ -1495,18 +1442,13 @@ class DirectSort : public SortBase<N> {
         int np = 1 << (sfhe::ilog2(num_partition / 2) >> 1);
         if (np * np > num_partition / 2) np >>= 1;
         auto output = this->getZero()->Clone();
-        Plaintext idx = maskMemo({2, 0, 0, (int)ctx_Rank->GetLevel(), N}, [&](auto& v) {
-            v.push_back(m_cc->MakeCKKSPackedPlaintext(generateIndexVector(), 1, ctx_Rank->GetLevel(), nullptr, N));
-        })[0];
-        auto indexMinusRank = m_cc->EvalSub(idx, ctx_Rank);
+        auto indexMinusRank = m_cc->EvalSub(indexPlain(ctx_Rank->GetLevel()), ctx_Rank);
         indexMinusRank->SetSlots(num_slots);
         input_array->SetSlots(num_slots);
         const int off = num_slots / N / 2;
         for (int b = 0; b < num_batch; ++b) {
-            Plaintext chk = maskMemo({10, b, 0, (int)indexMinusRank->GetLevel(), num_slots}, [&](auto& v) {
-                v.push_back(m_cc->MakeCKKSPackedPlaintext(generateCheckingVector2N(num_slots, b * off), 1,
-                                                          indexMinusRank->GetLevel(), nullptr, num_slots));
-            })[0];
+            const Plaintext& chk = memoPlain(kCheckingVector2N, b, 0, indexMinusRank->GetLevel(), num_slots,
+                                             [&] { return generateCheckingVector2N(num_slots, b * off); });
             // sinc on (i - rank - c) / 2N in (-1, 1)
             auto z = m_cc->EvalMult(m_cc->EvalSub(indexMinusRank, chk), 1.0 / N / 2);
             auto hit = m_cc->EvalChebyshevSeriesPS(z, selectCoefficients<N>(), -1, 1);
@@ -1537,30 +1479,119 @@ class DirectSort : public SortBase<N> {
         uint32_t level = 0, slots = 0;
         int func = -1, n = 0, dg = 0, df = 0;
         int multDepth = 0;  // decides whether compositeSign records bootstraps
+        bool stable = false;
+        std::vector<std::pair<uint32_t, uint32_t>> cols;  // records: each payload column's (level, slots)
         bool operator==(const GraphKey& o) const {
             return level == o.level && slots == o.slots && func == o.func && n == o.n && dg == o.dg && df == o.df &&
-                   multDepth == o.multDepth;
+                   multDepth == o.multDepth && stable == o.stable && cols == o.cols;
         }
     };
+    // The key of a sort of `first` (the input, or the records' key column) and
+    // the payload columns `cols`.  sort() leaves its input at S slots (:711): N
+    // and S select the same op sequence (rotation amounts < N), so they share
+    // a graph.
+    GraphKey graphKey(const Ciphertext<DCRTPoly>& first, const std::vector<Ciphertext<DCRTPoly>>& cols,
+                      SignFunc SignFunc, const SignConfig& Cfg, bool stable) {
+        const sfhe::RankLayout L(N, max_batch);
+        auto slotsOf = [&](const Ciphertext<DCRTPoly>& c) {
+            return c->GetSlots() == (uint32_t)L.S ? (uint32_t)N : c->GetSlots();
+        };
+        GraphKey key;
+        key.level = first->GetLevel();
+        key.slots = slotsOf(first);
+        key.func = (int)SignFunc;
+        key.n = Cfg.compos.n;
+        key.dg = Cfg.compos.dg;
+        key.df = Cfg.compos.df;
+        key.multDepth = Cfg.multDepth;
+        key.stable = stable;
+        for (const auto& c : cols) key.cols.emplace_back(c->GetLevel(), slotsOf(c));
+        return key;
+    }
     struct Graph {
         std::shared_ptr<CryptoContextImpl<DCRTPoly>::CapturedGraph> g;
-        Ciphertext<DCRTPoly> in, out;
+        std::vector<Ciphertext<DCRTPoly>> in, out;  // sorter-owned buffers (records: keys first)
         GraphKey key;
     };
-    // One cache per mode: a sorter may alternate plain and stable sorts, and
-    // each replays its own graph.
+    // One cache per mode: a sorter may alternate plain, stable and record
+    // sorts, and each replays its own graph.
     struct GraphCache {
         std::unique_ptr<Graph> graph;
         GraphKey warmKey;
         bool warm = false;
     };
-    GraphCache m_plain, m_stable;
+    GraphCache m_plain, m_stable, m_records;
     bool m_graphOff = false;
     bool m_lastStable = false;  // the mode of the last sort (graphNodes reports its graph)
 
     static bool graphsEnabled() {
         const char* v = std::getenv("SFHE_GRAPH");
         return !v || *v != '0';
+    }
+
+    // body() run inside a capture region, every output settled there: the
+    // graph must write their final rows (EndCapture settles the one it keeps).
+    // Null when the backend refuses or abandons the capture: nothing ran, and
+    // the sorter runs eagerly from then on, as after a body that throws.
+    template <class F>
+    std::shared_ptr<CryptoContextImpl<DCRTPoly>::CapturedGraph> captureRegion(F&& body,
+                                                                             std::vector<Ciphertext<DCRTPoly>>& out) {
+        if (m_cc->BeginCapture()) {
+            try {
+                out = body();
+                for (auto& o : out) m_cc->Settle(o);
+            } catch (...) {
+                m_cc->EndCapture(nullptr);
+                m_graphOff = true;
+                throw;
+            }
+            if (auto g = m_cc->EndCapture(out.back())) return g;
+        }
+        m_graphOff = true;
+        return nullptr;
+    }
+
+    // The graph protocol over one cache: the first call of a shape (key) runs
+    // eager(in), which generates and encodes the masks; the second captures
+    // eager over sorter-owned copies of the inputs; from then on a call copies
+    // the caller's inputs into those buffers, launches the graph and clones
+    // its outputs.  The callers' inputs get the slot counts eager leaves.
+    template <class F>
+    std::vector<Ciphertext<DCRTPoly>> runCached(GraphCache& cache, const GraphKey& key,
+                                                const std::vector<Ciphertext<DCRTPoly>>& in, F&& eager) {
+        std::unique_ptr<Graph>& graph = cache.graph;
+        if (!(graph && graph->key == key)) {
+            if (!(cache.warm && cache.warmKey == key)) {  // first call of this shape: eager, builds the masks
+                cache.warm = true;
+                cache.warmKey = key;
+                return eager(in);
+            }
+            graph.reset();
+            auto g = std::make_unique<Graph>();
+            g->key = key;
+            // sorter-owned input buffers (eager copies) in canonical form: a lazy
+            // product's pending rows would be rescaled into a new buffer
+            // INSIDE the graph, and replays would then ignore the copied-in input
+            for (const auto& c : in) {
+                m_cc->Settle(c);
+                g->in.push_back(c->Clone());
+                m_cc->Settle(g->in.back());
+            }
+            g->g = captureRegion([&] { return eager(g->in); }, g->out);
+            if (!g->g) return eager(in);
+            graph = std::move(g);
+        } else {
+            for (size_t c = 0; c < in.size(); ++c)
+                if (graph->in[c] != in[c]) m_cc->CopyCiphertextInto(graph->in[c], in[c]);
+        }
+        m_cc->Launch(graph->g);
+        std::vector<Ciphertext<DCRTPoly>> result;
+        for (size_t c = 0; c < in.size(); ++c) in[c]->SetSlots(graph->in[c]->GetSlots());  // eager's side effect (:711)
+        for (const auto& o : graph->out) {
+            result.push_back(o->Clone());
+            result.back()->SetSlots(o->GetSlots());
+        }
+        return result;
     }
 
   public:
@@ -1611,23 +1642,17 @@ class DirectSort : public SortBase<N> {
             m_cc->Settle(g->in);
             std::cout << "\n===== Direct Sort Input Array: \n";
             PRINT_PT(m_enc, input_array);
-            auto capture = [&](auto&& body, Ciphertext<DCRTPoly>& out)
-                -> std::shared_ptr<CryptoContextImpl<DCRTPoly>::CapturedGraph> {
-                if (!m_cc->BeginCapture()) return nullptr;
-                try {
-                    out = body();
-                } catch (...) {
-                    m_cc->EndCapture(nullptr);
-                    m_graphOff = true;
-                    throw;
+            auto capture = [&](auto&& body, Ciphertext<DCRTPoly>& out) {
+                std::vector<Ciphertext<DCRTPoly>> outs;
+                auto cg = captureRegion([&] { return std::vector<Ciphertext<DCRTPoly>>{body()}; }, outs);
+                if (cg) {
+                    out = outs[0];
+                    m_cc->Launch(cg);
                 }
-                auto cg = m_cc->EndCapture(out);
-                if (cg) m_cc->Launch(cg);
                 return cg;
             };
             g->rank = capture([&] { return constructRank(g->in, SignFunc, Cfg); }, g->rankOut);
             if (!g->rank) {  // (a capture that failed ran nothing: the rest eagerly)
-                m_graphOff = true;
                 auto ctx_Rank = constructRank(input_array, SignFunc, Cfg);
                 std::cout << "\n===== Constructed Rank: \n";
                 PRINT_PT(m_enc, ctx_Rank);
@@ -1644,7 +1669,6 @@ class DirectSort : public SortBase<N> {
             }
             g->place = capture([&] { return rotationIndexCheckN(g->rankOut, g->in); }, g->out);
             if (!g->place) {
-                m_graphOff = true;
                 auto output_array = rotationIndexCheckN(g->rankOut, input_array);
                 std::cout << "\n===== Final Output: \n";
                 PRINT_PT(m_enc, output_array);
@@ -1697,62 +1721,12 @@ class DirectSort : public SortBase<N> {
         // (a stable debug sort runs eagerly: the two-graph debug replay is the plain sort's)
         if (m_graphOff || !graphsEnabled() || (debug && stable))
             return sortEager(input_array, SignFunc, Cfg, stable);
-        GraphCache& cache = stable ? m_stable : m_plain;
-        std::unique_ptr<Graph>& m_graph = cache.graph;
-        GraphKey key;
-        key.level = input_array->GetLevel();
-        // sort() leaves its input at S slots (:711): N and S select the same
-        // op sequence (rotation amounts < N), so they share a graph
-        const sfhe::RankLayout L(N, max_batch);
-        key.slots = input_array->GetSlots() == (uint32_t)L.S ? (uint32_t)N : input_array->GetSlots();
-        key.func = (int)SignFunc;
-        key.n = Cfg.compos.n;
-        key.dg = Cfg.compos.dg;
-        key.df = Cfg.compos.df;
-        key.multDepth = Cfg.multDepth;
+        const GraphKey key = graphKey(input_array, {}, SignFunc, Cfg, stable);
         if (debug) return sortDebug(input_array, SignFunc, Cfg, key);
-        if (!(m_graph && m_graph->key == key)) {
-            if (!(cache.warm && cache.warmKey == key)) {  // first sort of this shape: eager, builds the masks
-                cache.warm = true;
-                cache.warmKey = key;
-                return sortEager(input_array, SignFunc, Cfg, stable);
-            }
-            m_graph.reset();
-            auto g = std::make_unique<Graph>();
-            g->key = key;
-            // sorter-owned input buffer (eager copy) in canonical form: a lazy
-            // product's pending rows would be rescaled into a new buffer
-            // INSIDE the graph, and replays would then ignore the copied-in input
-            m_cc->Settle(input_array);
-            g->in = input_array->Clone();
-            m_cc->Settle(g->in);
-            if (!m_cc->BeginCapture()) {
-                m_graphOff = true;
-                return sortEager(input_array, SignFunc, Cfg, stable);
-            }
-            Ciphertext<DCRTPoly> out;
-            try {
-                out = sortEager(g->in, SignFunc, Cfg, stable);
-            } catch (...) {
-                m_cc->EndCapture(nullptr);
-                m_graphOff = true;
-                throw;
-            }
-            g->g = m_cc->EndCapture(out);
-            if (!g->g) {
-                m_graphOff = true;
-                return sortEager(input_array, SignFunc, Cfg, stable);
-            }
-            g->out = out;
-            m_graph = std::move(g);
-        } else if (m_graph->in != input_array) {
-            m_cc->CopyCiphertextInto(m_graph->in, input_array);
-        }
-        m_cc->Launch(m_graph->g);
-        input_array->SetSlots(m_graph->in->GetSlots());  // sort()'s side effect on its input (:711)
-        auto result = m_graph->out->Clone();
-        result->SetSlots(m_graph->out->GetSlots());
-        return result;
+        return runCached(stable ? m_stable : m_plain, key, {input_array},
+                         [&](const std::vector<Ciphertext<DCRTPoly>>& in) {
+                             return std::vector<Ciphertext<DCRTPoly>>{sortEager(in[0], SignFunc, Cfg, stable)};
+                         })[0];
     }
 
     // ---- records: a key column and its payload columns sorted by the key ----
@@ -1760,30 +1734,9 @@ class DirectSort : public SortBase<N> {
     // cols...} (placeMany): first the sorted keys, then the sorted columns.
     // Payload values must lie in [-1, 1] like the keys: the placement's error
     // scales with |value|.  stable = true needs sfhe::stableSortDepth levels
-    // (constructRankStable's check and message).  Graphs follow sortMode's
-    // protocol with a cache of their own: the first call of a shape runs
-    // eagerly, the second is captured over 1 + C sorter-owned input buffers,
-    // later ones copy the inputs in and replay.
-    struct RecordsKey {
-        GraphKey base;
-        bool stable = false;
-        std::vector<std::pair<uint32_t, uint32_t>> cols;  // each column's (level, slots)
-        bool operator==(const RecordsKey& o) const {
-            return base == o.base && stable == o.stable && cols == o.cols;
-        }
-    };
-    struct RecordsGraph {
-        std::shared_ptr<CryptoContextImpl<DCRTPoly>::CapturedGraph> g;
-        std::vector<Ciphertext<DCRTPoly>> in, out;  // keys first
-        RecordsKey key;
-    };
-    struct RecordsCache {
-        std::unique_ptr<RecordsGraph> graph;
-        RecordsKey warmKey;
-        bool warm = false;
-    };
-    RecordsCache m_records;
-
+    // (constructRankStable's check and message).  Graphs follow the sort's
+    // protocol (runCached) with a cache of their own, over 1 + C sorter-owned
+    // input buffers.
     size_t recordsGraphNodes() const { return m_records.graph ? m_cc->GraphNodes(m_records.graph->g) : 0; }
 
     std::vector<Ciphertext<DCRTPoly>> sortRecordsEager(const std::vector<Ciphertext<DCRTPoly>>& in,
@@ -1807,77 +1760,19 @@ class DirectSort : public SortBase<N> {
         }
         const bool debug = dynamic_cast<const DebugEncryption*>(m_enc.get()) != nullptr;
         if (m_graphOff || !graphsEnabled() || debug) return sortRecordsEager(in, SignFunc, Cfg, stable);
-        const sfhe::RankLayout L(N, max_batch);
-        RecordsKey key;
-        key.base.level = keys->GetLevel();
-        key.base.func = (int)SignFunc;
-        key.base.n = Cfg.compos.n;
-        key.base.dg = Cfg.compos.dg;
-        key.base.df = Cfg.compos.df;
-        key.base.multDepth = Cfg.multDepth;
-        key.stable = stable;
-        // (N and S slots select the same op sequence, as in sortMode)
-        auto slotsOf = [&](const Ciphertext<DCRTPoly>& c) {
-            return c->GetSlots() == (uint32_t)L.S ? (uint32_t)N : c->GetSlots();
-        };
-        key.base.slots = slotsOf(keys);
-        for (const auto& c : cols) key.cols.emplace_back(c->GetLevel(), slotsOf(c));
-        std::unique_ptr<RecordsGraph>& graph = m_records.graph;
-        if (!(graph && graph->key == key)) {
-            if (!(m_records.warm && m_records.warmKey == key)) {  // first call of this shape: eager, builds the masks
-                m_records.warm = true;
-                m_records.warmKey = key;
-                return sortRecordsEager(in, SignFunc, Cfg, stable);
-            }
-            graph.reset();
-            auto g = std::make_unique<RecordsGraph>();
-            g->key = key;
-            // sorter-owned input buffers in canonical form (see sortMode)
-            for (const auto& c : in) {
-                m_cc->Settle(c);
-                g->in.push_back(c->Clone());
-                m_cc->Settle(g->in.back());
-            }
-            if (!m_cc->BeginCapture()) {
-                m_graphOff = true;
-                return sortRecordsEager(in, SignFunc, Cfg, stable);
-            }
-            std::vector<Ciphertext<DCRTPoly>> out;
-            try {
-                out = sortRecordsEager(g->in, SignFunc, Cfg, stable);
-                // every output's final rows are written inside the region
-                for (auto& o : out) m_cc->Settle(o);
-            } catch (...) {
-                m_cc->EndCapture(nullptr);
-                m_graphOff = true;
-                throw;
-            }
-            g->g = m_cc->EndCapture(out.back());
-            if (!g->g) {
-                m_graphOff = true;
-                return sortRecordsEager(in, SignFunc, Cfg, stable);
-            }
-            g->out = out;
-            graph = std::move(g);
-        } else {
-            for (size_t c = 0; c < in.size(); ++c)
-                if (graph->in[c] != in[c]) m_cc->CopyCiphertextInto(graph->in[c], in[c]);
-        }
-        m_cc->Launch(graph->g);
-        std::vector<Ciphertext<DCRTPoly>> result;
-        for (size_t c = 0; c < in.size(); ++c) {
-            in[c]->SetSlots(graph->in[c]->GetSlots());  // placeMany's side effect on its inputs
-            result.push_back(graph->out[c]->Clone());
-            result.back()->SetSlots(graph->out[c]->GetSlots());
-        }
-        return result;
+        return runCached(m_records, graphKey(keys, cols, SignFunc, Cfg, stable), in,
+                         [&](const std::vector<Ciphertext<DCRTPoly>>& cs) {
+                             return sortRecordsEager(cs, SignFunc, Cfg, stable);
+                         });
     }
 
+    // (the stable sort's depth was checked by sortStable: lexRank, not constructRankStable)
     Ciphertext<DCRTPoly> sortEager(const Ciphertext<DCRTPoly>& input_array, SignFunc SignFunc,
                                    SignConfig& Cfg, bool stable = false) {
         std::cout << "\n===== Direct Sort Input Array: \n";
         PRINT_PT(m_enc, input_array);
-        auto ctx_Rank = constructRankMode(input_array, SignFunc, Cfg, stable);
+        auto ctx_Rank = stable ? lexRank({input_array}, {false}, SignFunc, Cfg)
+                               : constructRank(input_array, SignFunc, Cfg);
         std::cout << "\n===== Constructed Rank: \n";
         PRINT_PT(m_enc, ctx_Rank);
         auto output_array = rotationIndexCheckN(ctx_Rank, input_array);
