@@ -977,15 +977,110 @@ class SfheInternal {
         s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
     }
 
+    // ---- relinearised products ------------------------------------------------
+    // Every product op of the engine ends in the same tail: a key-switch plan
+    // for the level (RelinPlan), one fused launch chain where the backend has
+    // it (fusedProduct), else the tensors (tensorSum) and relinRescale.
+
+    // env knob NAME set to 0 (read per call: tests switch these)
+    static bool knobOff(const char* name) {
+        const char* v = std::getenv(name);
+        return v && *v == '0';
+    }
+
+    // three polynomials of pw words, one after the other (a tensor's d0, d1, d2)
+    struct Rows3 {
+        uint64_t *d0, *d1, *d2;
+        DeviceBufferPtr buf;  // the allocation, where alloc3 made one
+    };
+    static Rows3 carve3(uint64_t* p, size_t pw) { return {p, p + pw, p + 2 * pw, nullptr}; }
+    static Rows3 alloc3(SfheContextState* s, size_t pw, size_t sets = 1) {
+        auto t = s->alloc(3 * pw * sets);
+        Rows3 r = carve3(t->ptr, pw);
+        r.buf = t;
+        return r;
+    }
+
+    // x's (c0, c1) rows over `ell` limbs: a prefix of its own, gathered (into
+    // keep) where x's rows are dealt over the ranks and ell limbs are replicated
+    static std::pair<const uint64_t*, const uint64_t*> rowsOver(SfheContextState* s, const Ct& x, uint32_t ell,
+                                                                std::vector<DeviceBufferPtr>& keep) {
+        if (!(s->shardAt(s->ellOf(x->level)) && !s->shardAt(ell))) return {x->c0, x->c1};
+        keep.push_back(gatherRows(s, x->c0, x->c1, ell));
+        return {keep.back()->ptr, keep.back()->ptr + (size_t)ell * s->n};
+    }
+
+    // consecutive indices of one key, at most batchWidth() of them: body(i, j) for each run [i, j)
+    template <class Key, class Body>
+    static void forRuns(size_t cnt, Key key, Body body) {
+        for (size_t i = 0, j; i < cnt; i = j) {
+            for (j = i + 1; j < cnt && j - i < batchWidth() && key(j) == key(i);) ++j;
+            body(i, j);
+        }
+    }
+
+    // m tensors of one level (the byte model is algorithmic: counted whichever form runs)
+    static void countTensors(SfheContextState* s, size_t m, uint32_t ell) {
+        s->stats.tensor += m;
+        s->countBytes(m * 7.0 * ell * s->n * 8);
+    }
+
     // A sum for the last pass of a product's rescale (prims.h sfp_*_add):
     // rows of a canonical ciphertext at the output level, added or
-    // subtracted, and / or per-row constants for c0.  done: the backend took it.
+    // subtracted, and / or per-row constants for c0 (k, owned here).  done:
+    // the backend took it.
     struct Fma {
         const uint64_t *r0 = nullptr, *r1 = nullptr;
         int sign = 1;
-        const uint64_t* cst = nullptr;
+        std::vector<u64> k;
         bool done = false;
-        explicit operator bool() const { return r0 || cst; }
+        Fma() = default;
+        // `add` for a product at `level`: its result is one level on
+        Fma(SfheContextState* s, const CC::MultAddend& add, uint32_t level) {
+            if (add.r) {
+                r0 = add.r->c0;
+                r1 = add.r->c1;
+                sign = add.sign;
+            }
+            if (add.c != 0.0) k = constResidues(s, add.c * s->scale[level + 1], s->ellOf(level) - 1);
+        }
+        const uint64_t* cst() const { return k.empty() ? nullptr : k.data(); }
+        explicit operator bool() const { return r0 || !k.empty(); }
+    };
+
+    // The relinearisation at `level`, looked up once per run of products: the
+    // key of its special-prime tier and what the ModDown and rescale need.
+    struct RelinPlan {
+        CC* cc;
+        SfheContextState* s;
+        uint32_t level, ell;
+        DeviceBufferPtr key;
+        int tier;
+        uint32_t K, beta;
+        size_t stride;  // words per accumulator polynomial: ell + K rows
+        sfp_conv* down;
+        const uint64_t *pinv, *pmod, *qlinv;
+        RelinPlan(CC* c, uint32_t lvl)
+            : cc(c), s(c->st.get()), level(lvl), ell(s->ellOf(lvl)), key(s->relinFor(ell)), tier(key->ksTier),
+              K(s->Kof(tier)), beta((ell + s->alpha - 1) / s->alpha), stride((size_t)(ell + K) * s->n),
+              down(s->moddownConvOf(tier)), pinv(s->pInvModQof(tier)), pmod(s->pModQof(tier)),
+              qlinv(s->qInvTable[ell].data()) {}  // (ell >= 2: the callers throw under their own names)
+        // one fused product's output and scratch
+        struct Work {
+            Ct out;
+            DeviceBufferPtr acc, ext, scratch;
+        };
+        Work work(uint32_t slots) const {
+            return {newCt(cc, level + 1, slots), s->alloc(2 * stride), s->alloc(stride * beta),
+                    s->alloc((size_t)2 * ell * s->n)};
+        }
+        // one key switch and one rescale, SURVEY §8(d): (3 l + 2 beta (l+K)) B and 4 l B
+        void counted() const {
+            s->stats.keyswitch++;
+            s->stats.rescale++;
+            s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * s->n * 8);
+            s->countBytes(4.0 * ell * s->n * 8);
+        }
     };
 
     // a sum the backend took: counted as the EvalAdd it replaces (the byte
@@ -1016,137 +1111,159 @@ class SfheInternal {
             keySwitchShard(cc, d2, ell, s->relinKey, d0, d1, 1, 1);
             return rescale(cc, d0, d1, level, slots);
         }
-        const DeviceBufferPtr& key = s->relinFor(ell);
-        const int tier = key->ksTier;
-        const uint32_t n = s->n, K = s->Kof(tier);
-        const uint32_t beta = (ell + s->alpha - 1) / s->alpha;
-        const size_t stride = (size_t)(ell + K) * n;
-        auto acc = s->alloc(2 * stride);
-        const int rowDone = modupInner(cc, acc->ptr, d2, ell, key, d0, d1, s->pModQof(tier)[ell - 1], 0, ell - 1);
+        const RelinPlan p(cc, level);
+        auto acc = s->alloc(2 * p.stride);
+        const int rowDone = modupInner(cc, acc->ptr, d2, ell, p.key, d0, d1, p.pmod[ell - 1], 0, ell - 1);
         Ct out = newCt(cc, level + 1, slots);
-        auto scratch = s->alloc((size_t)2 * (ell - 1) * n);
+        auto scratch = s->alloc((size_t)2 * (ell - 1) * s->n);
         if (f && *f && sfp_moddown_rescale_add &&
-            sfp_moddown_rescale_add(s->dev, out->c0, out->c1, d0, d1, acc->ptr, stride, ell, K, s->Lq,
-                                    s->moddownConvOf(tier), s->pInvModQof(tier), s->pModQof(tier),
-                                    s->qInvTable[ell].data(), scratch->ptr, rowDone, f->r0, f->r1, f->sign,
-                                    f->cst) == 0)
+            sfp_moddown_rescale_add(s->dev, out->c0, out->c1, d0, d1, acc->ptr, p.stride, ell, p.K, s->Lq, p.down,
+                                    p.pinv, p.pmod, p.qlinv, scratch->ptr, rowDone, f->r0, f->r1, f->sign,
+                                    f->cst()) == 0)
             f->done = true;
         else
-            sfp_moddown_rescale(s->dev, out->c0, out->c1, d0, d1, acc->ptr, stride, ell, K, s->Lq,
-                                s->moddownConvOf(tier), s->pInvModQof(tier), s->pModQof(tier),
-                                s->qInvTable[ell].data(), scratch->ptr, rowDone);
-        s->stats.keyswitch++;
-        s->stats.rescale++;
-        s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
-        s->countBytes(4.0 * ell * n * 8);
+            sfp_moddown_rescale(s->dev, out->c0, out->c1, d0, d1, acc->ptr, p.stride, ell, p.K, s->Lq, p.down, p.pinv,
+                                p.pmod, p.qlinv, scratch->ptr, rowDone);
+        p.counted();
         return out;
     }
 
-    // EvalMult(ct, ct)'s whole canonical tail from the aligned operands
-    // (a0, a1), (b0, b1) at `level`: one fused pass chain where the backend
-    // has it (sfp_mult_relin_rescale: the tensor is formed inside the key
-    // switch's passes, never written out), else the tensor then relinRescale.
-    static Ct multRelinRescale(CC* cc, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0,
-                               const uint64_t* b1, uint32_t level, uint32_t slots, Fma* f = nullptr) {
+    // The one place that names the fused product prims.  T: the operands' rows,
+    // (a0, a1, b0, b1) per term.  Plain: one product, sfp_mult_relin_rescale,
+    // or its _add form where f is taken (f->done); Sum2: two terms, sfp_mult2_*;
+    // SumN: m terms, sfp_multn_* (also for m = 1, 2).
+    enum class Flavour { Plain, Sum2, SumN };
+    // does the backend have the flavour's prim at all (the sums' are weak symbols)?
+    static bool haveFused(Flavour fl) {
+        return fl == Flavour::Plain || (fl == Flavour::Sum2 ? sfp_mult2_relin_rescale_add != nullptr
+                                                            : sfp_multn_relin_rescale_add != nullptr);
+    }
+
+    // Rescale(Relin(sum of m tensors)) (+ f) at p's level as one fused pass
+    // chain (the tensors are formed inside the key switch's passes, never
+    // written out), issued on `lane` of bs where given; counted.  Null, with
+    // nothing issued: the backend has no such form or declines, the level's
+    // rows are dealt over ranks, f's rows are not laid out as the output's.
+    static Ct fusedProduct(const RelinPlan& p, uint32_t slots, const uint64_t* const* T, uint32_t m, Fma* f,
+                           Flavour fl, BatchScope* bs = nullptr, uint32_t lane = 0) {
+        SfheContextState* s = p.s;
+        if (f && !*f) f = nullptr;
+        if (!haveFused(fl) || s->shardAt(p.ell) || (f && f->r0 && f->r1 - f->r0 != (ptrdiff_t)s->polyWords(p.level + 1)))
+            return nullptr;
+        auto& convs = modupConv(p.cc, p.ell, p.tier);
+        const auto w = p.work(slots);
+        if (bs) bs->lane(lane);
+        // prim(out, <operands>, the plan, the scratch, the addend)
+        auto withAddend = [&](auto prim, auto... operands) {
+            return prim(s->dev, w.out->c0, w.out->c1, operands..., p.ell, p.K, s->Lq, s->alpha, convs.data(),
+                        p.key->ptr, p.down, p.pinv, p.pmod, p.qlinv, w.acc->ptr, w.ext->ptr, w.scratch->ptr,
+                        f ? f->r0 : nullptr, f ? f->r1 : nullptr, f ? f->sign : 1, f ? f->cst() : nullptr);
+        };
+        int rc = -1;
+        if (fl == Flavour::SumN)
+            rc = withAddend(sfp_multn_relin_rescale_add, T, m);
+        else if (fl == Flavour::Sum2)
+            rc = withAddend(sfp_mult2_relin_rescale_add, T[0], T[1], T[2], T[3], T[4], T[5], T[6], T[7]);
+        else if (f && sfp_mult_relin_rescale_add)
+            rc = withAddend(sfp_mult_relin_rescale_add, T[0], T[1], T[2], T[3]);
+        if (rc == 0 && f) f->done = true;
+        if (rc != 0 && fl == Flavour::Plain)
+            rc = sfp_mult_relin_rescale(s->dev, w.out->c0, w.out->c1, T[0], T[1], T[2], T[3], p.ell, p.K, s->Lq,
+                                        s->alpha, convs.data(), p.key->ptr, p.down, p.pinv, p.pmod, p.qlinv,
+                                        w.acc->ptr, w.ext->ptr, w.scratch->ptr);
+        if (rc != 0) return nullptr;  // (no fused form: nothing issued)
+        p.counted();
+        return w.out;
+    }
+
+    // The composed form's tensors: sum_k (a_k0, a_k1) (x) (b_k0, b_k1) at
+    // `level`, each further term formed in the spare half and added component-wise
+    static Rows3 tensorSum(CC* cc, const uint64_t* const* T, uint32_t m, uint32_t level) {
         SfheContextState* s = cc->st.get();
-        const uint32_t ell = s->ellOf(level);
-        if (ell < 2) SFHE_THROW("no levels left to rescale (multiplicative depth exhausted)");
         const size_t pw = s->polyWords(level);
-        if (!s->shardAt(ell)) {
-            const DeviceBufferPtr& key = s->relinFor(ell);
-            const int tier = key->ksTier;
-            const uint32_t n = s->n, K = s->Kof(tier), beta = (ell + s->alpha - 1) / s->alpha;
-            const size_t stride = (size_t)(ell + K) * n;
-            Ct out = newCt(cc, level + 1, slots);
-            auto acc = s->alloc(2 * stride);
-            auto ext = s->alloc(stride * beta);
-            auto scratch = s->alloc((size_t)2 * ell * n);
-            auto& convs = modupConv(cc, ell, tier);
-            int rc = -1;
-            if (f && *f && sfp_mult_relin_rescale_add) {
-                rc = sfp_mult_relin_rescale_add(s->dev, out->c0, out->c1, a0, a1, b0, b1, ell, K, s->Lq, s->alpha,
-                                                convs.data(), key->ptr, s->moddownConvOf(tier),
-                                                s->pInvModQof(tier), s->pModQof(tier), s->qInvTable[ell].data(),
-                                                acc->ptr, ext->ptr, scratch->ptr, f->r0, f->r1, f->sign, f->cst);
-                if (rc == 0) f->done = true;
-            }
-            if (rc != 0)
-                rc = sfp_mult_relin_rescale(s->dev, out->c0, out->c1, a0, a1, b0, b1, ell, K, s->Lq, s->alpha,
-                                            convs.data(), key->ptr, s->moddownConvOf(tier), s->pInvModQof(tier),
-                                            s->pModQof(tier), s->qInvTable[ell].data(), acc->ptr, ext->ptr,
-                                            scratch->ptr);
-            if (rc == 0) {
-                s->stats.keyswitch++;
-                s->stats.rescale++;
-                s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
-                s->countBytes(4.0 * ell * n * 8);
-                return out;
-            }
+        const sfp_limbs lm = s->qmap(s->ellOf(level));
+        const Rows3 d = alloc3(s, pw, m > 1 ? 2 : 1), e = carve3(d.d0 + 3 * pw, pw);
+        for (uint32_t k = 0; k < m; ++k, T += 4) {
+            const Rows3& w = k ? e : d;
+            sfp_tensor(s->dev, w.d0, w.d1, w.d2, T[0], T[1], T[2], T[3], lm);
+            if (!k) continue;
+            sfp_add(s->dev, d.d0, d.d0, e.d0, lm);
+            sfp_add(s->dev, d.d1, d.d1, e.d1, lm);
+            sfp_add(s->dev, d.d2, d.d2, e.d2, lm);
         }
-        auto t = s->alloc(3 * pw);
-        uint64_t* d0 = t->ptr;
-        uint64_t* d1 = d0 + pw;
-        uint64_t* d2 = d1 + pw;
-        sfp_tensor(s->dev, d0, d1, d2, a0, a1, b0, b1, s->qmap(ell));
-        return relinRescale(cc, d0, d1, d2, level, slots, f);
+        return d;
     }
 
-    // multRelinRescale of up to SFP_BATCH_MAX independent operand pairs at one
-    // level as ONE batched op (sfp_batch_*): each pair's fused chain is issued
-    // on its own virtual lane and the pairs' identical launches run merged.
-    // Every pair's buffers live until the batch is issued.  Pairs the backend
-    // cannot fuse run one by one (multRelinRescale: the same values).
-    static std::vector<Ct> multRelinRescaleMany(CC* cc, const std::vector<const CiphertextImpl<DCRTPoly>*>& a,
-                                                const std::vector<const CiphertextImpl<DCRTPoly>*>& b, uint32_t level,
-                                                const std::vector<uint32_t>& slots, std::vector<Fma>* fs = nullptr) {
+    // One relinearised sum of products and the sum that may ride in its last pass
+    struct Product {
+        std::vector<const uint64_t*> T;  // (a0, a1, b0, b1) per term
+        uint32_t slots = 0;
+        Fma f;
+        const CC::MultAddend* add = nullptr;  // not yet translated: fusedBatch forms f from it as it issues the op
+        Ct out;
+    };
+    static void addTerm(Product& o, const Ct& a, const Ct& b) {
+        o.T.insert(o.T.end(), {a->c0, a->c1, b->c0, b->c1});
+        o.slots = std::max(o.slots, std::max(a->slots, b->slots));
+    }
+
+    // EvalMult(ct, ct)'s whole canonical tail from the aligned operands' rows
+    // T at `level`: the fused chain where the backend has it, else the tensor
+    // then relinRescale.  f: a sum for its last pass, taken where there is such a form.
+    static Ct multRelinRescale(CC* cc, const uint64_t* const* T, uint32_t level, uint32_t slots, Fma* f = nullptr) {
         SfheContextState* s = cc->st.get();
-        const size_t cnt = a.size();
-        const uint32_t ell = s->ellOf(level);
-        std::vector<Ct> out(cnt);
-        if (ell < 2) SFHE_THROW("no levels left to rescale (multiplicative depth exhausted)");
-        const DeviceBufferPtr& key = s->relinFor(ell);
-        const int tier = key->ksTier;
-        const uint32_t n = s->n, K = s->Kof(tier), beta = (ell + s->alpha - 1) / s->alpha;
-        const size_t stride = (size_t)(ell + K) * n;
-        auto& convs = modupConv(cc, ell, tier);
+        if (s->ellOf(level) < 2) SFHE_THROW("no levels left to rescale (multiplicative depth exhausted)");
+        if (!s->shardAt(s->ellOf(level)))
+            if (Ct out = fusedProduct(RelinPlan(cc, level), slots, T, 1, f, Flavour::Plain)) return out;
+        const Rows3 d = tensorSum(cc, T, 1, level);
+        return relinRescale(cc, d.d0, d.d1, d.d2, level, slots, f);
+    }
+
+    // The fused chains of up to SFP_BATCH_MAX independent products of m terms
+    // at p's level as ONE batched op (sfp_batch_*): each on its own virtual
+    // lane, their identical launches merged.  Where there is no batch (one op,
+    // SFHE_BATCH=0, an open batch or stacked region) the same chains are issued
+    // one after the other.  Stops at the first the backend declines; returns
+    // how many were issued.  The batch ends here: whatever the caller does for
+    // the rest runs as ordinary ops on its lane.
+    static size_t fusedBatch(const RelinPlan& p, std::vector<Product>& ops, uint32_t m, Flavour fl) {
+        BatchScope bs(p.cc, (uint32_t)ops.size());  // (callers keep dealt levels away: no fused form there)
         size_t done = 0;
-        {  // (the batch ends here: unfused pairs below run as ordinary ops on the caller's lane)
-        BatchScope bs(cc, s->shardAt(ell) ? 0 : (uint32_t)cnt);
-        if (bs) {
-            for (; done < cnt; ++done) {
-                out[done] = newCt(cc, level + 1, slots[done]);
-                auto acc = s->alloc(2 * stride);
-                auto ext = s->alloc(stride * beta);
-                auto scratch = s->alloc((size_t)2 * ell * n);
-                bs.lane((uint32_t)done);
-                Fma* f = fs && (*fs)[done] ? &(*fs)[done] : nullptr;
-                int rc = -1;
-                if (f && sfp_mult_relin_rescale_add) {
-                    rc = sfp_mult_relin_rescale_add(s->dev, out[done]->c0, out[done]->c1, a[done]->c0, a[done]->c1,
-                                                    b[done]->c0, b[done]->c1, ell, K, s->Lq, s->alpha, convs.data(),
-                                                    key->ptr, s->moddownConvOf(tier), s->pInvModQof(tier),
-                                                    s->pModQof(tier), s->qInvTable[ell].data(), acc->ptr, ext->ptr,
-                                                    scratch->ptr, f->r0, f->r1, f->sign, f->cst);
-                    if (rc == 0) f->done = true;
-                }
-                if (rc != 0)
-                    rc = sfp_mult_relin_rescale(s->dev, out[done]->c0, out[done]->c1, a[done]->c0, a[done]->c1,
-                                                b[done]->c0, b[done]->c1, ell, K, s->Lq, s->alpha, convs.data(),
-                                                key->ptr, s->moddownConvOf(tier), s->pInvModQof(tier),
-                                                s->pModQof(tier), s->qInvTable[ell].data(), acc->ptr, ext->ptr,
-                                                scratch->ptr);
-                if (rc != 0) break;  // (no fused form: nothing issued for this pair)
-                s->stats.keyswitch++;
-                s->stats.rescale++;
-                s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
-                s->countBytes(4.0 * ell * n * 8);
-            }
+        for (; done < ops.size(); ++done) {
+            Product& o = ops[done];
+            if (o.add) o.f = Fma(p.s, *o.add, p.level);
+            if (!(o.out = fusedProduct(p, o.slots, o.T.data(), m, &o.f, fl, &bs, (uint32_t)done))) break;
         }
-        }
-        for (size_t i = done; i < cnt; ++i)
-            out[i] = multRelinRescale(cc, a[i]->c0, a[i]->c1, b[i]->c0, b[i]->c1, level, slots[i],
-                                      fs ? &(*fs)[i] : nullptr);
-        return out;
+        return done;
+    }
+
+    // multRelinRescale of a run of independent pairs at one level: batched,
+    // then one by one from the first pair the backend cannot fuse (the same values)
+    static void multRelinRescaleMany(CC* cc, uint32_t level, std::vector<Product>& ops) {
+        SfheContextState* s = cc->st.get();
+        if (s->ellOf(level) < 2) SFHE_THROW("no levels left to rescale (multiplicative depth exhausted)");
+        const bool dealt = s->shardAt(s->ellOf(level));  // (no fused form there: no plan either)
+        for (size_t i = dealt ? 0 : fusedBatch(RelinPlan(cc, level), ops, 1, Flavour::Plain); i < ops.size(); ++i)
+            ops[i].out = multRelinRescale(cc, ops[i].T.data(), level, ops[i].slots, &ops[i].f);
+    }
+
+    // prod (+|-) r (+ c) as the separate ops
+    static Ct addAfter(CC* cc, Ct prod, const CC::MultAddend& add) {
+        if (add.r) prod = add.sign < 0 ? cc->EvalSub(prod, add.r) : cc->EvalAdd(prod, add.r);
+        if (add.c != 0.0) prod = cc->EvalAdd(prod, add.c);
+        return prod;
+    }
+    // ... unless the product's last pass took the sum (f.done): then only counted
+    static Ct sumAfter(CC* cc, const Ct& prod, const Fma& f, const CC::MultAddend& add, uint32_t level) {
+        if (!f.done) return addAfter(cc, prod, add);
+        countFused(cc->st.get(), add, cc->st->ellOf(level) - 1);
+        return prod;
+    }
+    // the eager canonical product of the aligned a and b (EvalMult, EvalMultAdd)
+    static Ct multTraced(CC* cc, const Ct& a, const Ct& b, Fma* f = nullptr) {
+        Product o;
+        addTerm(o, a, b);
+        return traced(cc, multRelinRescale(cc, o.T.data(), a->level, o.slots, f), "EvalMult");
     }
 
     // gal != 0 (hoisted rotations, unsharded levels): ext is the unpermuted
@@ -1951,7 +2068,8 @@ struct DeferredRelin : DeferredOp {
         s->dep(pa.get());
         s->dep(pb.get());
         if (!pending) {
-            SfheInternal::adopt(ct, SfheInternal::multRelinRescale(cc, a0, a1, b0, b1, level, slots));
+            const uint64_t* T[4] = {a0, a1, b0, b1};
+            SfheInternal::adopt(ct, SfheInternal::multRelinRescale(cc, T, level, slots));
             return;
         }
         const size_t pw = s->polyWords(level);
@@ -3163,9 +3281,7 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMult(const Ciphertext<DCRT
     SfheInternal::align(this, a, b);
     const uint32_t ell = s->ellOf(a->level);
     if (ell < 2) SFHE_THROW("no levels left (multiplicative depth exhausted)");
-    const size_t pw = s->polyWords(a->level);
-    s->stats.tensor++;
-    s->countBytes(7.0 * ell * s->n * 8);
+    SfheInternal::countTensors(s, 1, ell);
     const uint32_t slots = std::max(a->slots, b->slots);
     if (SfheInternal::lazy(s) && SfheInternal::fusedRescale()) {
         auto op = std::make_shared<DeferredRelin>();
@@ -3179,16 +3295,12 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMult(const Ciphertext<DCRT
         op->slots = slots;
         return SfheInternal::deferredCt(this, a->level + 1, slots, op);
     }
-    if (SfheInternal::fusedRescale())
-        return SfheInternal::traced(
-            this, SfheInternal::multRelinRescale(this, a->c0, a->c1, b->c0, b->c1, a->level, slots), "EvalMult");
-    auto t = s->alloc(3 * pw);
-    uint64_t* d0 = t->ptr;
-    uint64_t* d1 = d0 + pw;
-    uint64_t* d2 = d1 + pw;
-    sfp_tensor(s->dev, d0, d1, d2, a->c0, a->c1, b->c0, b->c1, st->qmap(ell));
-    SfheInternal::keySwitch(this, d2, ell, s->relinFor(ell), d0, d1, 1, 1);
-    return SfheInternal::traced(this, SfheInternal::rescale(this, d0, d1, a->level, slots), "EvalMult");
+    if (SfheInternal::fusedRescale()) return SfheInternal::multTraced(this, a, b);
+    SfheInternal::Product o;
+    SfheInternal::addTerm(o, a, b);
+    const auto d = SfheInternal::tensorSum(this, o.T.data(), 1, a->level);
+    SfheInternal::keySwitch(this, d.d2, ell, s->relinFor(ell), d.d0, d.d1, 1, 1);
+    return SfheInternal::traced(this, SfheInternal::rescale(this, d.d0, d.d1, a->level, slots), "EvalMult");
 }
 
 Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalSquare(const Ciphertext<DCRTPoly>& a) {
@@ -3213,12 +3325,8 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalTieTerm(const Ciphertext<D
     const auto kr = SfheInternal::constResidues(s, k * a->scale * s->scale[level + 1], ell);
     const size_t pw = s->polyWords(level);
     const sfp_limbs m = s->qmap(ell);
-    auto t = s->alloc(3 * pw);
-    uint64_t* d0 = t->ptr;
-    uint64_t* d1 = d0 + pw;
-    uint64_t* d2 = d1 + pw;
-    const char* knob = std::getenv("SFHE_TIE_FUSED");  // (read per call: tests switch it)
-    const bool fused = sfp_tie_tensor && !(knob && *knob == '0') && !s->shardAt(ell) &&
+    const auto [d0, d1, d2, t] = SfheInternal::alloc3(s, pw);
+    const bool fused = sfp_tie_tensor && !SfheInternal::knobOff("SFHE_TIE_FUSED") && !s->shardAt(ell) &&
                        sfp_tie_tensor(s->dev, d0, d1, d2, a->c0, a->c1, w, kr.data(), m) == 0;
     if (fused) {
         s->stats.tie_fused++;
@@ -3260,28 +3368,14 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalLexStep(const Ciphertext<D
     // v's and q's rows over u's limbs: a prefix of their own, gathered where
     // theirs are dealt over the ranks and u's level is replicated
     std::vector<DeviceBufferPtr> keep;
-    auto rowsOf = [&](const Ciphertext<DCRTPoly>& x, const uint64_t*& x0, const uint64_t*& x1) {
-        x0 = x->c0;
-        x1 = x->c1;
-        if (s->shardAt(s->ellOf(x->level)) && !s->shardAt(ell)) {
-            keep.push_back(SfheInternal::gatherRows(s, x->c0, x->c1, ell));
-            x0 = keep.back()->ptr;
-            x1 = x0 + (size_t)ell * s->n;
-        }
-    };
-    const uint64_t *v0, *v1, *q0, *q1;
-    rowsOf(v, v0, v1);
-    rowsOf(q, q0, q1);
+    const auto [v0, v1] = SfheInternal::rowsOver(s, v, ell, keep);
+    const auto [q0, q1] = SfheInternal::rowsOver(s, q, ell, keep);
     const auto kr = SfheInternal::constResidues(s, q->scale, ell);
     const auto lr = SfheInternal::constResidues(s, q->scale * u->scale / v->scale, ell);
     const size_t pw = s->polyWords(level);
     const sfp_limbs m = s->qmap(ell);
-    auto t = s->alloc(3 * pw);
-    uint64_t* d0 = t->ptr;
-    uint64_t* d1 = d0 + pw;
-    uint64_t* d2 = d1 + pw;
-    const char* knob = std::getenv("SFHE_LEX_FUSED");  // (read per call: tests switch it)
-    const bool fused = sfp_lex_tensor && !(knob && *knob == '0') && !s->shardAt(ell) &&
+    const auto [d0, d1, d2, t] = SfheInternal::alloc3(s, pw);
+    const bool fused = sfp_lex_tensor && !SfheInternal::knobOff("SFHE_LEX_FUSED") && !s->shardAt(ell) &&
                        sfp_lex_tensor(s->dev, d0, d1, d2, v0, v1, q0, q1, u->c0, u->c1, kr.data(), lr.data(), m) == 0;
     if (fused) {
         s->stats.lex_fused++;
@@ -3354,22 +3448,14 @@ std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalGateSumMany(
     // an operand's rows over q's limbs: a prefix of its own, gathered where its
     // rows are dealt over the ranks and q's level is replicated (EvalLexStep)
     std::vector<DeviceBufferPtr> keep;
-    auto rowsOf = [&](const Ciphertext<DCRTPoly>& x, const uint64_t*& x0, const uint64_t*& x1) {
-        x0 = x->c0;
-        x1 = x->c1;
-        if (s->shardAt(s->ellOf(x->level)) && !s->shardAt(ell)) {
-            keep.push_back(SfheInternal::gatherRows(s, x->c0, x->c1, ell));
-            x0 = keep.back()->ptr;
-            x1 = x0 + (size_t)ell * s->n;
-        }
-    };
     std::vector<const uint64_t*> q0(nb), q1(nb), u0(nc * nb), u1(nc * nb);
     for (size_t b = 0; b < nb; ++b) {
         q0[b] = q[b]->c0;
         q1[b] = q[b]->c1;
     }
     for (size_t c = 0; c < nc; ++c)
-        for (size_t b = 0; b < nb; ++b) rowsOf(u[c][b], u0[c * nb + b], u1[c * nb + b]);
+        for (size_t b = 0; b < nb; ++b)
+            std::tie(u0[c * nb + b], u1[c * nb + b]) = SfheInternal::rowsOver(s, u[c][b], ell, keep);
     const auto kr = SfheInternal::constResidues(s, q[0]->scale, ell);
     const size_t pw = s->polyWords(level);
     const sfp_limbs m = s->qmap(ell);
@@ -3380,8 +3466,8 @@ std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalGateSumMany(
         d1[c] = d0[c] + pw;
         d2[c] = d1[c] + pw;
     }
-    const char* knob = std::getenv("SFHE_GROUP_FUSED");  // (read per call: tests switch it)
-    const bool fused = sfp_gate_tensor_cols && !(knob && *knob == '0') && !s->shardAt(ell) && nb <= SFP_GATE_MAX_B &&
+    const bool fused = sfp_gate_tensor_cols && !SfheInternal::knobOff("SFHE_GROUP_FUSED") && !s->shardAt(ell) &&
+                       nb <= SFP_GATE_MAX_B &&
                        sfp_gate_tensor_cols(s->dev, d0.data(), d1.data(), d2.data(), q0.data(), q1.data(), u0.data(),
                                             u1.data(), kr.data(), (uint32_t)nb, (uint32_t)nc, m) == 0;
     if (fused) {
@@ -3425,58 +3511,6 @@ std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalGateSumMany(
     return out;
 }
 
-std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultMany(
-    const std::vector<Ciphertext<DCRTPoly>>& a0, const std::vector<Ciphertext<DCRTPoly>>& b0) {
-    OpLock g(st.get());
-    SfheContextState* s = st.get();
-    if (a0.size() != b0.size()) SFHE_THROW("operand count mismatch");
-    const size_t cnt = a0.size();
-    std::vector<Ciphertext<DCRTPoly>> out(cnt);
-    // the products are formed canonically (as a deferred product is when its
-    // consumer needs the canonical form: the same values); for consumers that
-    // would take a lazy product's pending rows, use EvalMult
-    if (cnt < 2 || !SfheInternal::fusedRescale()) {
-        for (size_t i = 0; i < cnt; ++i) out[i] = EvalMult(a0[i], b0[i]);
-        return out;
-    }
-    if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalMult");
-    std::vector<Ciphertext<DCRTPoly>> A(a0), B(b0);
-    for (size_t i = 0; i < cnt; ++i) {
-        SfheInternal::deps(s, {&a0[i], &b0[i]});
-        SfheInternal::align(this, A[i], B[i]);
-        if (s->ellOf(A[i]->level) < 2) SFHE_THROW("no levels left (multiplicative depth exhausted)");
-        s->stats.tensor++;
-        s->countBytes(7.0 * s->ellOf(A[i]->level) * s->n * 8);
-    }
-    // runs of up to SFP_BATCH_MAX consecutive pairs at one level
-    for (size_t i = 0; i < cnt;) {
-        size_t j = i + 1;
-        while (j < cnt && j - i < batchWidth() && A[j]->level == A[i]->level) ++j;
-        std::vector<const CiphertextImpl<DCRTPoly>*> pa, pb;
-        std::vector<uint32_t> slots;
-        for (size_t k = i; k < j; ++k) {
-            pa.push_back(A[k].get());
-            pb.push_back(B[k].get());
-            slots.push_back(std::max(A[k]->slots, B[k]->slots));
-        }
-        auto r = SfheInternal::multRelinRescaleMany(this, pa, pb, A[i]->level, slots);
-        for (size_t k = i; k < j; ++k) out[k] = SfheInternal::traced(this, r[k - i], "EvalMult");
-        i = j;
-    }
-    return out;
-}
-
-// ---- a product with the sum that follows it (the polynomial evaluators) ----
-namespace {
-// prod (+|-) r (+ c) as today's separate ops
-Ciphertext<DCRTPoly> addAfter(CryptoContextImpl<DCRTPoly>* cc, Ciphertext<DCRTPoly> prod,
-                              const CryptoContextImpl<DCRTPoly>::MultAddend& add) {
-    if (add.r) prod = add.sign < 0 ? cc->EvalSub(prod, add.r) : cc->EvalAdd(prod, add.r);
-    if (add.c != 0.0) prod = cc->EvalAdd(prod, add.c);
-    return prod;
-}
-}  // namespace
-
 // Can `add` ride in the last pass of the product of a and b (the conditions
 // of EvalMultAdd, openfhe.h)?
 bool CryptoContextImpl<DCRTPoly>::multAddFusable(const Ciphertext<DCRTPoly>& a, const Ciphertext<DCRTPoly>& b,
@@ -3497,41 +3531,76 @@ bool CryptoContextImpl<DCRTPoly>::multAddFusable(const Ciphertext<DCRTPoly>& a, 
     return true;
 }
 
+// EvalMultMany and EvalMultManyAdd (adds: one per pair) past their entry
+// conditions: every product canonical, consecutive pairs of one level as
+// batched ops, each sum in its product's last pass where it can ride there
+std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::multMany(const std::vector<Ciphertext<DCRTPoly>>& a0,
+                                                                        const std::vector<Ciphertext<DCRTPoly>>& b0,
+                                                                        const std::vector<MultAddend>* adds,
+                                                                        const char* who) {
+    SfheContextState* s = st.get();
+    auto fail = [&](const char* msg) { throw OpenFHEException(std::string(who) + ": " + msg); };
+    if (!s->relinKey) fail("EvalMultKeyGen must be called before EvalMult");
+    const size_t cnt = a0.size();
+    std::vector<Ciphertext<DCRTPoly>> out(cnt), A(a0), B(b0);
+    std::vector<char> fuse(cnt);
+    for (size_t i = 0; i < cnt; ++i) {
+        fuse[i] = adds && multAddFusable(a0[i], b0[i], (*adds)[i]);
+        SfheInternal::deps(s, {&a0[i], &b0[i]});
+        if (fuse[i]) SfheInternal::deps(s, {&(*adds)[i].r});
+        SfheInternal::align(this, A[i], B[i]);
+        if (s->ellOf(A[i]->level) < 2) fail("no levels left (multiplicative depth exhausted)");
+        SfheInternal::countTensors(s, 1, s->ellOf(A[i]->level));
+    }
+    // runs of up to SFP_BATCH_MAX consecutive pairs at one level
+    SfheInternal::forRuns(cnt, [&](size_t i) { return A[i]->level; }, [&](size_t i, size_t j) {
+        const uint32_t level = A[i]->level;
+        std::vector<SfheInternal::Product> run(j - i);
+        for (size_t k = i; k < j; ++k) {
+            SfheInternal::addTerm(run[k - i], A[k], B[k]);
+            if (fuse[k]) run[k - i].f = SfheInternal::Fma(s, (*adds)[k], level);
+        }
+        SfheInternal::multRelinRescaleMany(this, level, run);
+        for (size_t k = i; k < j; ++k) {
+            out[k] = SfheInternal::traced(this, run[k - i].out, "EvalMult");
+            if (adds) out[k] = SfheInternal::sumAfter(this, out[k], run[k - i].f, (*adds)[k], level);
+        }
+    });
+    return out;
+}
+
+std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultMany(
+    const std::vector<Ciphertext<DCRTPoly>>& a0, const std::vector<Ciphertext<DCRTPoly>>& b0) {
+    OpLock g(st.get());
+    if (a0.size() != b0.size()) SFHE_THROW("operand count mismatch");
+    // the products are formed canonically (as a deferred product is when its
+    // consumer needs the canonical form: the same values); for consumers that
+    // would take a lazy product's pending rows, use EvalMult
+    if (a0.size() >= 2 && SfheInternal::fusedRescale()) return multMany(a0, b0, nullptr, __func__);
+    std::vector<Ciphertext<DCRTPoly>> out(a0.size());
+    for (size_t i = 0; i < a0.size(); ++i) out[i] = EvalMult(a0[i], b0[i]);
+    return out;
+}
+
+// ---- a product with the sum that follows it (the polynomial evaluators) ----
 Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMultAdd(const Ciphertext<DCRTPoly>& a0,
                                                              const Ciphertext<DCRTPoly>& b0,
                                                              const MultAddend& add) {
     OpLock g(st.get());
-    if (!multAddFusable(a0, b0, add)) return addAfter(this, EvalMult(a0, b0), add);
+    if (!multAddFusable(a0, b0, add)) return SfheInternal::addAfter(this, EvalMult(a0, b0), add);
     SfheContextState* s = st.get();
     SfheInternal::deps(s, {&a0, &b0, &add.r});
     auto a = a0, b = b0;
     SfheInternal::align(this, a, b);
-    const uint32_t ell = s->ellOf(a->level), slots = std::max(a->slots, b->slots);
-    s->stats.tensor++;
-    s->countBytes(7.0 * ell * s->n * 8);
-    std::vector<uint64_t> k;
-    SfheInternal::Fma f;
-    if (add.r) {
-        f.r0 = add.r->c0;
-        f.r1 = add.r->c1;
-        f.sign = add.sign;
-    }
-    if (add.c != 0.0) {
-        k = SfheInternal::constResidues(s, add.c * s->scale[a->level + 1], ell - 1);
-        f.cst = k.data();
-    }
-    auto out = SfheInternal::traced(
-        this, SfheInternal::multRelinRescale(this, a->c0, a->c1, b->c0, b->c1, a->level, slots, &f), "EvalMult");
-    if (!f.done) return addAfter(this, out, add);
-    SfheInternal::countFused(s, add, ell - 1);
-    return out;
+    SfheInternal::countTensors(s, 1, s->ellOf(a->level));
+    SfheInternal::Fma f(s, add, a->level);
+    return SfheInternal::sumAfter(this, SfheInternal::multTraced(this, a, b, &f), f, add, a->level);
 }
 
 std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultManyAdd(
     const std::vector<Ciphertext<DCRTPoly>>& a0, const std::vector<Ciphertext<DCRTPoly>>& b0,
     const std::vector<MultAddend>& adds) {
     OpLock g(st.get());
-    SfheContextState* s = st.get();
     if (a0.size() != b0.size() || a0.size() != adds.size()) SFHE_THROW("operand count mismatch");
     const size_t cnt = a0.size();
     std::vector<Ciphertext<DCRTPoly>> out(cnt);
@@ -3539,59 +3608,11 @@ std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultManyAdd(
         for (size_t i = 0; i < cnt; ++i) out[i] = EvalMultAdd(a0[i], b0[i], adds[i]);
         return out;
     }
-    if (!psFma() || !SfheInternal::fusedRescale() || SfheInternal::lazy(s)) {
-        // nothing can be folded: the batched products as EvalMultMany forms them, then the sums
-        out = EvalMultMany(a0, b0);
-        for (size_t i = 0; i < cnt; ++i) out[i] = addAfter(this, out[i], adds[i]);
-        return out;
-    }
-    if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalMult");
-    std::vector<Ciphertext<DCRTPoly>> A(a0), B(b0);
-    std::vector<char> fuse(cnt);
-    for (size_t i = 0; i < cnt; ++i) {
-        fuse[i] = multAddFusable(a0[i], b0[i], adds[i]);
-        SfheInternal::deps(s, {&a0[i], &b0[i]});
-        if (fuse[i]) SfheInternal::deps(s, {&adds[i].r});
-        SfheInternal::align(this, A[i], B[i]);
-        if (s->ellOf(A[i]->level) < 2) SFHE_THROW("no levels left (multiplicative depth exhausted)");
-        s->stats.tensor++;
-        s->countBytes(7.0 * s->ellOf(A[i]->level) * s->n * 8);
-    }
-    // runs of up to SFP_BATCH_MAX consecutive pairs at one level (EvalMultMany)
-    for (size_t i = 0; i < cnt;) {
-        size_t j = i + 1;
-        while (j < cnt && j - i < batchWidth() && A[j]->level == A[i]->level) ++j;
-        const uint32_t level = A[i]->level, ell = s->ellOf(level);
-        std::vector<const CiphertextImpl<DCRTPoly>*> pa, pb;
-        std::vector<uint32_t> slots;
-        std::vector<SfheInternal::Fma> fs(j - i);
-        std::vector<std::vector<uint64_t>> ks(j - i);
-        for (size_t k = i; k < j; ++k) {
-            pa.push_back(A[k].get());
-            pb.push_back(B[k].get());
-            slots.push_back(std::max(A[k]->slots, B[k]->slots));
-            if (!fuse[k]) continue;
-            SfheInternal::Fma& f = fs[k - i];
-            if (adds[k].r) {
-                f.r0 = adds[k].r->c0;
-                f.r1 = adds[k].r->c1;
-                f.sign = adds[k].sign;
-            }
-            if (adds[k].c != 0.0) {
-                ks[k - i] = SfheInternal::constResidues(s, adds[k].c * s->scale[level + 1], ell - 1);
-                f.cst = ks[k - i].data();
-            }
-        }
-        auto r = SfheInternal::multRelinRescaleMany(this, pa, pb, level, slots, &fs);
-        for (size_t k = i; k < j; ++k) {
-            out[k] = SfheInternal::traced(this, r[k - i], "EvalMult");
-            if (fs[k - i].done)
-                SfheInternal::countFused(s, adds[k], ell - 1);
-            else
-                out[k] = addAfter(this, out[k], adds[k]);
-        }
-        i = j;
-    }
+    if (psFma() && SfheInternal::fusedRescale() && !SfheInternal::lazy(st.get()))
+        return multMany(a0, b0, &adds, __func__);
+    // nothing can be folded: the batched products as EvalMultMany forms them, then the sums
+    out = EvalMultMany(a0, b0);
+    for (size_t i = 0; i < cnt; ++i) out[i] = SfheInternal::addAfter(this, out[i], adds[i]);
     return out;
 }
 
@@ -3619,51 +3640,28 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalMultSum2(const Ciphertext<
     if (r && (r->level != level + 1 || r->scale != s->scale[level + 1]))
         SFHE_THROW("EvalMultSum2: the addend is not canonical at the result's level " + std::to_string(level + 1));
     SfheInternal::deps(s, {&a, &b, &a2, &b2, &r});
-    const uint32_t n = s->n;
-    uint32_t slots = std::max(std::max(a->slots, b->slots), std::max(a2->slots, b2->slots));
-    if (r) slots = std::max(slots, r->slots);
-    const size_t pw = s->polyWords(level);
-    s->stats.tensor += 2;
-    s->countBytes(2 * 7.0 * ell * n * 8);
-    const char* knob = std::getenv("SFHE_MULT_SUM2_FUSED");  // (read per call: tests switch it)
-    if (sfp_mult2_relin_rescale_add && !(knob && *knob == '0') && SfheInternal::fusedRescale() && !s->shardAt(ell) &&
-        (!r || r->c1 - r->c0 == (ptrdiff_t)s->polyWords(level + 1))) {
-        const DeviceBufferPtr& key = s->relinFor(ell);
-        const int tier = key->ksTier;
-        const uint32_t K = s->Kof(tier), beta = (ell + s->alpha - 1) / s->alpha;
-        const size_t stride = (size_t)(ell + K) * n;
-        auto out = SfheInternal::newCt(this, level + 1, slots);
-        auto acc = s->alloc(2 * stride);
-        auto ext = s->alloc(stride * beta);
-        auto scratch = s->alloc((size_t)2 * ell * n);
-        auto& convs = SfheInternal::modupConv(this, ell, tier);
-        if (sfp_mult2_relin_rescale_add(s->dev, out->c0, out->c1, a->c0, a->c1, b->c0, b->c1, a2->c0, a2->c1, b2->c0,
-                                        b2->c1, ell, K, s->Lq, s->alpha, convs.data(), key->ptr,
-                                        s->moddownConvOf(tier), s->pInvModQof(tier), s->pModQof(tier),
-                                        s->qInvTable[ell].data(), acc->ptr, ext->ptr, scratch->ptr,
-                                        r ? r->c0 : nullptr, r ? r->c1 : nullptr, 1, nullptr) == 0) {
-            s->stats.dot_fused++;
-            s->stats.keyswitch++;
-            s->stats.rescale++;
-            s->stats.add += r ? 2 : 1;
-            s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
-            s->countBytes(4.0 * ell * n * 8);
-            return SfheInternal::traced(this, out, "EvalMultSum2");
-        }
+    // the m-term path with its own knob, counters and addend accounting: the
+    // fused form counts the addend in `add` only, the composed one adds it with EvalAdd
+    SfheInternal::Product p;
+    SfheInternal::addTerm(p, a, b);
+    SfheInternal::addTerm(p, a2, b2);
+    if (r) p.slots = std::max(p.slots, r->slots);
+    p.f = SfheInternal::Fma(s, MultAddend{r, 1, 0.0}, level);
+    SfheInternal::countTensors(s, 2, ell);
+    if (!SfheInternal::knobOff("SFHE_MULT_SUM2_FUSED") && SfheInternal::fusedRescale() && !s->shardAt(ell) &&
+        (p.out = SfheInternal::fusedProduct(SfheInternal::RelinPlan(this, level), p.slots, p.T.data(), 2, &p.f,
+                                            SfheInternal::Flavour::Sum2))) {
+        s->stats.dot_fused++;
+        s->stats.add += r ? 2 : 1;
+        return SfheInternal::traced(this, p.out, "EvalMultSum2");
     }
     // composed: both tensors, their components summed, one relinearisation + rescale, then the addend
-    auto t = s->alloc(6 * pw);
-    uint64_t* d = t->ptr;
-    uint64_t* e = d + 3 * pw;
-    const sfp_limbs m = s->qmap(ell);
-    sfp_tensor(s->dev, d, d + pw, d + 2 * pw, a->c0, a->c1, b->c0, b->c1, m);
-    sfp_tensor(s->dev, e, e + pw, e + 2 * pw, a2->c0, a2->c1, b2->c0, b2->c1, m);
-    for (int i = 0; i < 3; ++i) sfp_add(s->dev, d + i * pw, d + i * pw, e + i * pw, m);
+    const auto d = SfheInternal::tensorSum(this, p.T.data(), 2, level);
     s->stats.add++;
     s->stats.dot_composed++;
-    auto out = SfheInternal::relinRescale(this, d, d + pw, d + 2 * pw, level, slots);
-    if (r) out = EvalAdd(out, r);  // (both canonical at one level: one sfp_add)
-    return SfheInternal::traced(this, out, "EvalMultSum2");
+    p.out = SfheInternal::relinRescale(this, d.d0, d.d1, d.d2, level, p.slots);
+    if (r) p.out = EvalAdd(p.out, r);  // (both canonical at one level: one sfp_add)
+    return SfheInternal::traced(this, p.out, "EvalMultSum2");
 }
 
 // The sum of m products at one level, relinearised and rescaled once.
@@ -3701,97 +3699,47 @@ std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalMultSumMany(c
     SfheContextState* s = st.get();
     if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalMultSum");
     const size_t cnt = ops.size();
-    const uint32_t n = s->n;
     std::vector<Ciphertext<DCRTPoly>> out(cnt);
-    std::vector<uint32_t> slots(cnt);
-    for (size_t o = 0; o < cnt; ++o) {
-        if (const char* why = MultSumViolation(ops[o])) SFHE_THROW(std::string("EvalMultSum: ") + why);
-        slots[o] = ops[o].add.r ? ops[o].add.r->slots : 0;
-        for (const MultTerm& t : ops[o].terms)
-            slots[o] = std::max(slots[o], std::max(t.first->slots, t.second->slots));
-    }
+    for (const MultSumOp& op : ops)
+        if (const char* why = MultSumViolation(op)) SFHE_THROW(std::string("EvalMultSum: ") + why);
+    auto levelOf = [&](size_t o) { return ops[o].terms[0].first->level; };
     for (size_t o = 0; o < cnt; ++o) {
         for (const MultTerm& t : ops[o].terms) SfheInternal::deps(s, {&t.first, &t.second});
         SfheInternal::deps(s, {&ops[o].add.r});
-        const size_t m = ops[o].terms.size();
-        s->stats.tensor += m;
-        s->countBytes(m * 7.0 * s->ellOf(ops[o].terms[0].first->level) * n * 8);
+        SfheInternal::countTensors(s, ops[o].terms.size(), s->ellOf(levelOf(o)));
     }
-    const char* knob = std::getenv("SFHE_MULT_SUM_FUSED");  // (read per call: tests switch it)
-    const bool fusedOn = sfp_multn_relin_rescale_add && !(knob && *knob == '0') && SfheInternal::fusedRescale();
+    const bool fusedOn = SfheInternal::haveFused(SfheInternal::Flavour::SumN) &&
+                         !SfheInternal::knobOff("SFHE_MULT_SUM_FUSED") && SfheInternal::fusedRescale();
     // runs of up to BatchWidth() consecutive ops of one level and one term count
-    for (size_t i = 0; i < cnt;) {
-        const uint32_t level = ops[i].terms[0].first->level, ell = s->ellOf(level);
-        const size_t m = ops[i].terms.size();
-        size_t j = i + 1;
-        while (j < cnt && j - i < batchWidth() && ops[j].terms[0].first->level == level && ops[j].terms.size() == m) ++j;
-        const size_t pw = s->polyWords(level);
-        size_t done = i;
+    auto key = [&](size_t o) { return std::make_pair(levelOf(o), ops[o].terms.size()); };
+    SfheInternal::forRuns(cnt, key, [&](size_t i, size_t j) {
+        const uint32_t level = levelOf(i), m = (uint32_t)ops[i].terms.size();
+        std::vector<SfheInternal::Product> run(j - i);
+        for (size_t o = i; o < j; ++o) {
+            SfheInternal::Product& p = run[o - i];
+            for (const MultTerm& t : ops[o].terms) SfheInternal::addTerm(p, t.first, t.second);
+            if (ops[o].add.r) p.slots = std::max(p.slots, ops[o].add.r->slots);
+            p.add = &ops[o].add;
+        }
         s->stats.sumn_batches++;
-        if (fusedOn && !s->shardAt(ell)) {
-            const DeviceBufferPtr& key = s->relinFor(ell);
-            const int tier = key->ksTier;
-            const uint32_t K = s->Kof(tier), beta = (ell + s->alpha - 1) / s->alpha;
-            const size_t stride = (size_t)(ell + K) * n;
-            auto& convs = SfheInternal::modupConv(this, ell, tier);
-            std::vector<std::vector<uint64_t>> ks(j - i);
-            BatchScope bs(this, (uint32_t)(j - i));  // (the batch ends with this block: the composed ops follow it)
-            for (; done < j; ++done) {
-                const MultSumOp& op = ops[done];
-                const auto& r = op.add.r;
-                if (r && r->c1 - r->c0 != (ptrdiff_t)s->polyWords(level + 1)) break;
-                std::vector<const uint64_t*> rows;
-                for (const MultTerm& t : op.terms)
-                    for (const uint64_t* p : {(const uint64_t*)t.first->c0, (const uint64_t*)t.first->c1,
-                                              (const uint64_t*)t.second->c0, (const uint64_t*)t.second->c1})
-                        rows.push_back(p);
-                const uint64_t* cst = nullptr;
-                if (op.add.c != 0.0) {
-                    ks[done - i] = SfheInternal::constResidues(s, op.add.c * s->scale[level + 1], ell - 1);
-                    cst = ks[done - i].data();
-                }
-                auto res = SfheInternal::newCt(this, level + 1, slots[done]);
-                auto acc = s->alloc(2 * stride);
-                auto ext = s->alloc(stride * beta);
-                auto scratch = s->alloc((size_t)2 * ell * n);
-                bs.lane((uint32_t)(done - i));
-                if (sfp_multn_relin_rescale_add(s->dev, res->c0, res->c1, rows.data(), (uint32_t)m, ell, K, s->Lq,
-                                                s->alpha, convs.data(), key->ptr, s->moddownConvOf(tier),
-                                                s->pInvModQof(tier), s->pModQof(tier), s->qInvTable[ell].data(),
-                                                acc->ptr, ext->ptr, scratch->ptr, r ? r->c0 : nullptr,
-                                                r ? r->c1 : nullptr, op.add.sign, cst) != 0)
-                    break;  // (declined: nothing issued for this op)
+        size_t done = 0;
+        if (fusedOn && !s->shardAt(s->ellOf(level)))
+            done = SfheInternal::fusedBatch(SfheInternal::RelinPlan(this, level), run, m, SfheInternal::Flavour::SumN);
+        for (size_t o = i; o < j; ++o) {
+            SfheInternal::Product& p = run[o - i];
+            if (m > 1) s->stats.add++;  // (the tensors' sum)
+            if (o - i < done) {
                 s->stats.sumn_fused++;
-                s->stats.keyswitch++;
-                s->stats.rescale++;
-                if (m > 1) s->stats.add++;
-                SfheInternal::countFused(s, op.add, ell - 1);
-                s->countBytes((3.0 * ell + 2.0 * beta * (ell + K)) * n * 8);
-                s->countBytes(4.0 * ell * n * 8);
-                out[done] = SfheInternal::traced(this, res, "EvalMultSum");
+                SfheInternal::countFused(s, ops[o].add, s->ellOf(level) - 1);
+            } else {  // composed: the tensors summed, one relinearisation + rescale, then the addend
+                const auto d = SfheInternal::tensorSum(this, p.T.data(), m, level);
+                s->stats.sumn_composed++;
+                p.out = SfheInternal::addAfter(this, SfheInternal::relinRescale(this, d.d0, d.d1, d.d2, level, p.slots),
+                                               ops[o].add);
             }
+            out[o] = SfheInternal::traced(this, p.out, "EvalMultSum");
         }
-        // composed: the tensors, their components summed, one relinearisation + rescale, then the addend
-        for (size_t o = done; o < j; ++o) {
-            const MultSumOp& op = ops[o];
-            auto t = s->alloc(6 * pw);
-            uint64_t* d = t->ptr;
-            uint64_t* e = d + 3 * pw;
-            const sfp_limbs lm = s->qmap(ell);
-            for (size_t k = 0; k < m; ++k) {
-                const MultTerm& x = op.terms[k];
-                uint64_t* w = k ? e : d;
-                sfp_tensor(s->dev, w, w + pw, w + 2 * pw, x.first->c0, x.first->c1, x.second->c0, x.second->c1, lm);
-                if (k)
-                    for (int c = 0; c < 3; ++c) sfp_add(s->dev, d + c * pw, d + c * pw, e + c * pw, lm);
-            }
-            if (m > 1) s->stats.add++;
-            s->stats.sumn_composed++;
-            auto res = SfheInternal::relinRescale(this, d, d + pw, d + 2 * pw, level, slots[o]);
-            out[o] = SfheInternal::traced(this, addAfter(this, res, op.add), "EvalMultSum");
-        }
-        i = j;
-    }
+    });
     return out;
 }
 
@@ -3866,9 +3814,8 @@ std::vector<std::vector<Ciphertext<DCRTPoly>>> CryptoContextImpl<DCRTPoly>::Eval
     std::vector<std::vector<Ciphertext<DCRTPoly>>> out(nc);
     for (size_t c = 0; c < nc; ++c)
         for (size_t k = 0; k < ng; ++k) out[c].push_back(EvalMultAddPlain(a[c], *p[k]));
-    const char* knob = std::getenv("SFHE_PLACE_COLS");  // (read per call: tests switch it)
-    bool fuse = sfp_mac_plain2_cols && !(knob && *knob == '0') && nin <= SFP_MAC_MULTI_N && ng <= SFP_MAC_COLS_G &&
-                nc <= SFP_MAC_COLS_C;
+    bool fuse = sfp_mac_plain2_cols && !SfheInternal::knobOff("SFHE_PLACE_COLS") && nin <= SFP_MAC_MULTI_N &&
+                ng <= SFP_MAC_COLS_G && nc <= SFP_MAC_COLS_C;
     std::vector<DeferredMacPlain*> macs;
     for (size_t c = 0; c < nc && fuse; ++c)
         for (size_t k = 0; k < ng && fuse; ++k) {

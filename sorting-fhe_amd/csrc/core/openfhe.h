@@ -838,6 +838,10 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
 
   private:
     bool multAddFusable(const Ciphertext<DCRTPoly>& a, const Ciphertext<DCRTPoly>& b, const MultAddend& add) const;
+    // the shared body of EvalMultMany (adds null) and EvalMultManyAdd; who: the caller, for messages
+    std::vector<Ciphertext<DCRTPoly>> multMany(const std::vector<Ciphertext<DCRTPoly>>& a,
+                                               const std::vector<Ciphertext<DCRTPoly>>& b,
+                                               const std::vector<MultAddend>* adds, const char* who);
     std::unique_ptr<SfheContextState> st;
     uint32_t enabled = 0;
     BootstrapTap bootTap;

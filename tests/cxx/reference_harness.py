@@ -70,7 +70,8 @@ PROGRAMS = {
 }
 
 # the engine's own test programs (no reference sources; always buildable)
-OWN = {"fherma_client": os.path.join(HERE, "fherma_client.cpp")}
+OWN = {"fherma_client": os.path.join(HERE, "fherma_client.cpp"),
+       "product_counters": os.path.join(HERE, "product_counters.cpp")}
 
 
 def _engine_mtime() -> float:
@@ -83,10 +84,13 @@ def _engine_mtime() -> float:
     return t
 
 
-def build_own():
+def build_own(backends=None):
+    """The engine's own programs against every library, or those of `backends` only."""
     built = {}
     for name, src in OWN.items():
         for backend, (libdir, lib) in LIBS.items():
+            if backends is not None and backend not in backends:
+                continue
             exe = os.path.join(OUT, f"{name}_{backend}")
             os.makedirs(OUT, exist_ok=True)
             if not _fresh(exe, src):
