@@ -43,7 +43,8 @@ extern "C" {
  * sfhe_eval_mult_sum, sfhe_eval_mult_sum_many, sfhe_sumn_counts,
  * sfhe_sumn_batch_counts, sfhe_ct_relabel_scale, and the grouping by a key:
  * sfhe_group_params, sfhe_sorter_group, sfhe_eval_gate_sum_many,
- * sfhe_group_counts) */
+ * sfhe_group_counts, and the window sums: SFHE_FRAME_*, sfhe_window_params,
+ * sfhe_sorter_window, sfhe_eval_weight_sum_many, sfhe_window_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -473,6 +474,49 @@ int sfhe_sorter_group(sfhe_sorter* s, const sfhe_ct* keys, const sfhe_ct* const*
 int sfhe_eval_gate_sum_many(sfhe_ctx* c, const sfhe_ct* const* q, size_t nq, const sfhe_ct* const* u, size_t ncols,
                             sfhe_ct** outs);
 int sfhe_group_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
+/* Engine extensions (additions at ABI 3): aggregates over an ordered frame --
+ * SUM(col) OVER (ORDER BY key) with ROW_NUMBER(), RANK() and CUME_DIST() --
+ * every result in the rows' input order, with no placement.  `keys` and the
+ * 0 <= ncols <= SFHE_MAX_COLUMNS payload columns (values in [-1, 1]) sit at one
+ * level and slot count.  Row j is in row r's frame where
+ *   SFHE_FRAME_ROWS   (key_j, j) <= (key_r, r): ROWS UNBOUNDED PRECEDING ..
+ *                     CURRENT ROW in stable order
+ *   SFHE_FRAME_RANGE  key_j <= key_r: SQL's default frame, peers included
+ *   SFHE_FRAME_BELOW  key_j < key_r
+ * sums_out[c]: slot r holds column c's sum over row r's frame.  *count
+ * (want_count != 0; else set to NULL and `count` may be NULL): slot r holds the
+ * number of rows in the frame -- ROW_NUMBER() under rows, N CUME_DIST() under
+ * range, RANK() - 1 under below.  *count is one level above the sums, which
+ * end at the context's sfhe_window_params depth: the stable rank's plus one.
+ * Two keys must be equal or at least the sign configuration's resolution apart
+ * (1/N for the defaults).
+ * sfhe_window_params: the mult_depth of sfhe_sorter_window with N's default
+ * sign configuration and the rotation amounts it uses: sfhe_group_params'.
+ * An unknown frame, a column count out of range, a NULL entry or columns at
+ * another level or slot count than the key: SFHE_EINVAL; too little depth:
+ * SFHE_ESCHEME, the message naming the depth needed, before anything is
+ * computed.  Always eager. */
+#define SFHE_FRAME_ROWS 0
+#define SFHE_FRAME_RANGE 1
+#define SFHE_FRAME_BELOW 2
+int sfhe_window_params(uint32_t N, uint32_t* mult_depth, int32_t* rotations, size_t cap, size_t* count);
+int sfhe_sorter_window(sfhe_sorter* s, const sfhe_ct* keys, const sfhe_ct* const* cols, size_t ncols, int frame,
+                       int want_count, int n, int dg, int df, sfhe_ct** count, sfhe_ct** sums_out);
+/* outs[c] = sum_b (weights[b] + v[b]) (.) u[c * nv + b], relinearised once per
+ * column, one level below v: the window sums' weighted column sums.  The nv >= 1
+ * gates sit at one level and scale; weights[b] holds `len` doubles, encoded as
+ * sfhe_eval_mult_plain encodes its values but at v's scale, so the sum with
+ * v[b] is exact; an operand may have more limbs than the gates (a numerically
+ * lower level), a column's operands share one scale; 0 <= ncols <=
+ * SFHE_MAX_COLUMNS.  A NULL entry, gates at different levels, an operand at a
+ * numerically higher level than the gates or a count out of range: SFHE_EINVAL.
+ * sfhe_window_counts: such calls whose tensors ran as fused launches
+ * (sfp_weight_tensor_cols) and as the composed generic prims since the last
+ * sfhe_op_stats reset (SFHE_WINDOW_FUSED=0, read per call, composes; the
+ * results are bit-identical). */
+int sfhe_eval_weight_sum_many(sfhe_ctx* c, const sfhe_ct* const* v, size_t nv, const double* const* weights,
+                              size_t len, uint32_t slots, const sfhe_ct* const* u, size_t ncols, sfhe_ct** outs);
+int sfhe_window_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
 /* nodes of the captured record sort (0 while none); sfhe_sorter_graph_nodes
  * keeps reporting the plain / stable sort's graph */
 int sfhe_sorter_records_graph_nodes(const sfhe_sorter* s, uint64_t* nodes);

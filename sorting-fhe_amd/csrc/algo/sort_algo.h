@@ -28,6 +28,8 @@
 // place / select the keys and payload columns by it.
 // Grouping: groupAggregate gives every row the size of its
 // key's group, its number inside the group and the group's column sums.
+// Window sums: windowSums gives every row, in input order, the
+// running count and column sums over the rows before it in key order.
 // What these methods share is written once: runBatches (the batches over
 // lanes and batch groups), sumOverPartitions (batch sum and folds),
 // sfhe::SincIndicator (the placements' and selections' indicator), MemoTag and
@@ -135,6 +137,9 @@ inline int lexSortDepth(int N, const CompositeSignConfig& c, int m) { return sta
 // Grouping by a key: 1 (mask) + sign + 1 (q = s^2) + 1 (the
 // gated product, or the index mask): the stable rank's levels and no placement.
 inline int groupDepth(const CompositeSignConfig& c) { return stableRankDepth(c); }
+// Window sums over an ordered frame: the stable rank's tie
+// term as the gate, then 1 (the gated product); no placement.
+inline int windowDepth(const CompositeSignConfig& c) { return stableRankDepth(c) + 1; }
 
 // getSizeParameters' (depth, rotation keys) for N (reference :87-201);
 // nullptr when the reference has no entry.
@@ -452,7 +457,10 @@ class DirectSort : public SortBase<N> {
         kTargets = 13,           // targetPlain [b, target list]
         kMoveMasks = 14,         // moveMasks [target list, 1024 b + g]
         kBeforeMask = 15,        // groupAggregate's M_b [b]
-        kGroupIndex = 16         // groupAggregate's index vector
+        kGroupIndex = 16,        // groupAggregate's index vector
+        kWindowWeights = 17,     // windowSums' W_b = -w_b [frame, b]
+        kWindowGate = 18,        // windowSums' p_b = 1/2 + w_b [frame, b]
+        kWindowCount = 19        // windowSums' K [frame]
     };
     std::map<std::array<int, 5>, std::vector<Plaintext>> m_masks;
     std::mutex m_masksMu;  // the batches' host threads share the memo
@@ -838,6 +846,121 @@ class DirectSort : public SortBase<N> {
             out.index = m_cc->EvalSub(indexPlain(before->GetLevel(), kGroupIndex), before);
         }
         ph.mark("group: count + index");
+        return out;
+    }
+
+    // ---- aggregates over an ordered frame (SUM(col) OVER (ORDER BY key),
+    // ROW_NUMBER(), RANK(), CUME_DIST()) ----
+    enum WindowFrame : int {
+        kFrameRows = 0,   // (key_j, j) <= (key_r, r): ROWS UNBOUNDED PRECEDING .. CURRENT ROW in stable order
+        kFrameRange = 1,  // key_j <= key_r: SQL's default frame, peers included
+        kFrameBelow = 2   // key_j < key_r
+    };
+    struct WindowResult {
+        Ciphertext<DCRTPoly> count;              // count_r = #{j in row r's frame}; null unless asked for
+        std::vector<Ciphertext<DCRTPoly>> sums;  // sums[c]_r = sum of cols[c]_j over row r's frame
+    };
+    // w of the frame in slot pN + r of batch b (d = bP + p, j = (r + d) mod N):
+    // a tie counts where w = +1/2 and does not where w = -1/2
+    static double windowWeight(int frame, int r, int d) {
+        if (frame == kFrameRange) return 0.5;
+        if (frame == kFrameBelow) return -0.5;
+        return d == 0 || r + d >= N ? 0.5 : -0.5;  // rows: the self slot and j < r
+    }
+    // sign * w (sign = -1: W_b) or 1/2 + w (sign = 0: p_b) over batch b's slots
+    std::vector<double> generateWindowWeights(int num_slots, int num_partition, int b, int frame, int sign) {
+        std::vector<double> v(num_slots);
+        for (int p = 0; p < num_slots / N; ++p)
+            for (int r = 0; r < N; ++r) {
+                const double w = windowWeight(frame, r, b * num_partition + p);
+                v[(size_t)p * N + r] = sign ? sign * w : 0.5 + w;
+            }
+        return v;
+    }
+    // In constructRankStable's slot layout with no self offset (the self slot
+    // is a tie like any other, groupAggregate), s_b the composite sign of
+    // key_r - key_j and u_bc column c's value at row j in the same layout:
+    //   v_b     = EvalTieTerm(s_b, W_b, 1/2),  W_b = -w_b     two levels below the sign
+    //   g_b     = p_b + v_b,  p_b = 1/2 + w_b                 the 0/1 indicator "row j is in row r's frame"
+    //   sum_cr  = fold(sum_b g_b (.) u_bc)_r                   one level below v
+    //   count_r = K_r + fold(sum_b v_b)_r,  K_r = sum_d p      at v's level
+    // The frames differ in w alone (windowWeight).  Per batch on its lane:
+    // vecRotsOpt of the key and of every column (shared masks), the sign and
+    // the tie term; after the join ONE EvalWeightSumMany for all batches and
+    // columns and the rank's doubling folds, as groupAggregate.  Depth
+    // windowDepth: the stable rank's plus the gated product; the count ends one
+    // level above the sums.  Eager (no graph).  Preconditions: two keys are
+    // equal or at least the sign configuration's resolution apart; payload
+    // values lie in [-1, 1].
+    WindowResult windowSums(const Ciphertext<DCRTPoly>& keys, const std::vector<Ciphertext<DCRTPoly>>& cols,
+                            SignFunc SignFunc, SignConfig& Cfg, int frame, bool wantCount, size_t maxCols) {
+        const size_t C = cols.size();
+        if (frame != kFrameRows && frame != kFrameRange && frame != kFrameBelow)
+            throw std::invalid_argument("window: unknown frame " + std::to_string(frame) +
+                                        " (0 rows, 1 range, 2 below)");
+        if (C > maxCols)
+            throw std::invalid_argument("window: " + std::to_string(C) + " payload columns (at most " +
+                                        std::to_string(maxCols) + ")");
+        for (const auto& c : cols)
+            if (c->GetLevel() != keys->GetLevel() || c->GetSlots() != keys->GetSlots())
+                throw std::invalid_argument("window: the key and the columns must be at one level and slot count");
+        const int need = (int)keys->GetLevel() + sfhe::windowDepth(Cfg.compos);
+        if ((int)m_cc->GetMultiplicativeDepth() < need)
+            throw OpenFHEException("window: needs multiplicative depth " + std::to_string(need) +
+                                   " (the stable rank's and one level for the gated product); the context has " +
+                                   std::to_string(m_cc->GetMultiplicativeDepth()));
+        const sfhe::RankLayout L(N, max_batch);
+        sfhe::PhaseTimer ph(m_cc);
+        const auto pre = rankBabyRotations(keys, L);
+        std::vector<std::vector<Ciphertext<DCRTPoly>>> preCols(C);
+        for (size_t c = 0; c < C; ++c) preCols[c] = rankBabyRotations(cols[c], L);
+        ph.mark("window: baby rotations");
+
+        std::vector<Ciphertext<DCRTPoly>> v(L.B);
+        std::vector<std::vector<Ciphertext<DCRTPoly>>> u(C, std::vector<Ciphertext<DCRTPoly>>(L.B));
+        const auto split = runBatches(L.B, [&](int b) {
+            auto shifted = vecRotsOpt(pre, L.P, L.S, L.npRank, b);
+            for (size_t c = 0; c < C; ++c) u[c][b] = vecRotsOpt(preCols[c], L.P, L.S, L.npRank, b);
+            ph.mark("  window batch: vecRotsOpt");
+            auto dup = keys->Clone();
+            dup->SetSlots(L.S);
+            auto s = sign(m_cc->EvalSub(dup, shifted), m_cc, SignFunc, Cfg);
+            const Plaintext& W = memoPlain(kWindowWeights, frame, b, s->GetLevel(), L.S,
+                                           [&] { return generateWindowWeights(L.S, L.P, b, frame, -1); });
+            v[b] = m_cc->EvalTieTerm(s, W, 0.5);
+            ph.mark("  window batch: sign + tie term");
+        });
+        split.gatherParts(m_cc, v);
+        for (auto& col : u) split.gatherParts(m_cc, col);
+        ph.mark("window: batches");
+
+        auto fold = [&](Ciphertext<DCRTPoly> x) {
+            x->SetSlots(L.S);
+            return sumOverPartitions(x, {}, L.S);
+        };
+        WindowResult out;
+        if (C) {
+            std::vector<Plaintext> p(L.B);
+            for (int b = 0; b < L.B; ++b)
+                p[b] = memoPlain(kWindowGate, frame, b, v[b]->GetLevel(), L.S,
+                                 [&] { return generateWindowWeights(L.S, L.P, b, frame, 0); });
+            out.sums = m_cc->EvalWeightSumMany(v, p, u);
+            for (auto& x : out.sums) x = fold(x);
+        }
+        ph.mark("window: weighted sums + folds");
+        if (wantCount) {
+            auto acc = v[0]->Clone();
+            for (int b = 1; b < L.B; ++b) m_cc->EvalAddInPlace(acc, v[b]);
+            acc = fold(acc);
+            const Plaintext& K = memoPlain(kWindowCount, frame, 0, acc->GetLevel(), N, [&] {
+                std::vector<double> k(N, 0.0);
+                for (int r = 0; r < N; ++r)
+                    for (int d = 0; d < N; ++d) k[r] += 0.5 + windowWeight(frame, r, d);
+                return k;
+            });
+            out.count = m_cc->EvalAdd(acc, K);
+        }
+        ph.mark("window: count");
         return out;
     }
 

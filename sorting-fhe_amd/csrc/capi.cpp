@@ -118,6 +118,9 @@ struct SorterBase {
                                              SignConfig& cfg) = 0;
     // {count, index (null unless asked for), sums...}
     virtual std::vector<Ct> group(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, bool wantIndex) = 0;
+    // {count (null unless asked for), sums...}
+    virtual std::vector<Ct> window(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, int frame,
+                                   bool wantCount) = 0;
     virtual Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) = 0;
     virtual Ct hybrid(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk, int variant) = 0;
     virtual Ct place2N(const Ct& rank, const Ct& in) = 0;
@@ -187,6 +190,13 @@ struct Sorter : SorterBase {
     std::vector<Ct> group(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, bool wantIndex) override {
         auto r = ds.groupAggregate(keys, cols, SignFunc::CompositeSign, cfg, wantIndex, SFHE_MAX_COLUMNS);
         std::vector<Ct> out{r.count, r.index};
+        out.insert(out.end(), r.sums.begin(), r.sums.end());
+        return out;
+    }
+    std::vector<Ct> window(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, int frame,
+                           bool wantCount) override {
+        auto r = ds.windowSums(keys, cols, SignFunc::CompositeSign, cfg, frame, wantCount, SFHE_MAX_COLUMNS);
+        std::vector<Ct> out{r.count};
         out.insert(out.end(), r.sums.begin(), r.sums.end());
         return out;
     }
@@ -468,6 +478,14 @@ int sfhe_group_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
     auto s = c->cc->GetOpStats();
     *fused = s.gate_fused;
     *composed = s.gate_composed;
+    return SFHE_OK;
+}
+
+int sfhe_window_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
+    REQUIRE(c && fused && composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *fused = s.weight_fused;
+    *composed = s.weight_composed;
     return SFHE_OK;
 }
 
@@ -1044,6 +1062,80 @@ int sfhe_eval_gate_sum_many(sfhe_ctx* c, const sfhe_ct* const* q, size_t nq, con
         for (size_t k = 0; k < ncols; ++k)
             for (size_t b = 0; b < nq; ++b) us[k].push_back(u[k * nq + b]->ct);
         auto got = c->cc->EvalGateSumMany(qs, us);
+        for (size_t k = 0; k < ncols; ++k) outs[k] = wrap(got[k]);
+    });
+}
+
+// the rank's amounts in the layout of the size table's ring (2^17): baby steps,
+// giant steps, the batches' offsets and the partition folds.  A smaller ring
+// uses a subset of them or composes its own from them.
+static std::set<int> rankRotations(uint32_t N) {
+    const sfhe::RankLayout L((int)N, 1 << 16);
+    std::set<int> r;
+    for (int i = 1; i < L.npRank; ++i) r.insert(i);
+    for (int j = 1; j < L.P / L.npRank; ++j) r.insert(j * L.npRank);
+    for (int b = 1; b < L.B; ++b) r.insert(b * L.P);
+    for (int sft = L.S / 2; sft >= (int)N; sft /= 2) r.insert(sft);
+    return r;
+}
+
+int sfhe_window_params(uint32_t N, uint32_t* mult_depth, int32_t* rot, size_t cap, size_t* count) {
+    REQUIRE(validN(N), "N must be a power of two in [4, 1024]");
+    return guard([&] {
+        const std::set<int> r = rankRotations(N);
+        if (mult_depth) *mult_depth = (uint32_t)sfhe::windowDepth(sfhe::defaultSignConfig((int)N));
+        if (count) *count = r.size();
+        size_t i = 0;
+        for (int v : r) {
+            if (i >= cap || !rot) break;
+            rot[i++] = v;
+        }
+    });
+}
+
+int sfhe_sorter_window(sfhe_sorter* s, const sfhe_ct* keys, const sfhe_ct* const* cols, size_t ncols, int frame,
+                       int want_count, int n, int dg, int df, sfhe_ct** count, sfhe_ct** sums_out) {
+    REQUIRE(s && keys && (!want_count || count) && (ncols == 0 || (cols && sums_out)), "null argument");
+    REQUIRE(ncols <= SFHE_MAX_COLUMNS, "column count out of range (0 .. SFHE_MAX_COLUMNS)");
+    REQUIRE(frame >= SFHE_FRAME_ROWS && frame <= SFHE_FRAME_BELOW, "unknown frame (0 rows, 1 range, 2 below)");
+    for (size_t i = 0; i < ncols; ++i) REQUIRE(cols[i], "null column");
+    return guard([&] {
+        auto cfg = cfgOf(n, dg, df);
+        std::vector<Ct> in;
+        for (size_t i = 0; i < ncols; ++i) in.push_back(cols[i]->ct);
+        auto got = s->impl->window(keys->ct, in, cfg, frame, want_count != 0);
+        if (count) *count = want_count ? wrap(got[0]) : nullptr;
+        for (size_t i = 0; i < ncols; ++i) sums_out[i] = wrap(got[1 + i]);
+    });
+}
+
+int sfhe_eval_weight_sum_many(sfhe_ctx* c, const sfhe_ct* const* v, size_t nv, const double* const* weights,
+                              size_t len, uint32_t slots, const sfhe_ct* const* u, size_t ncols, sfhe_ct** outs) {
+    REQUIRE(c && v && weights && (ncols == 0 || (u && outs)), "null argument");
+    REQUIRE(nv >= 1, "no gates");
+    REQUIRE(ncols <= SFHE_MAX_COLUMNS, "column count out of range (0 .. SFHE_MAX_COLUMNS)");
+    for (size_t b = 0; b < nv; ++b) {
+        REQUIRE(v[b], "null gate");
+        REQUIRE(weights[b] || !len, "null weight vector");
+        REQUIRE(v[b]->ct->GetLevel() == v[0]->ct->GetLevel(), "the gates must be at one level");
+    }
+    for (size_t i = 0; i < ncols * nv; ++i) {
+        REQUIRE(u[i], "null operand");
+        REQUIRE(u[i]->ct->GetLevel() <= v[0]->ct->GetLevel(),
+                "the operands must have at least the gates' limbs (a level not above the gates')");
+    }
+    return guard([&] {
+        std::vector<Ct> vs;
+        std::vector<Plaintext> ps;
+        for (size_t b = 0; b < nv; ++b) {
+            vs.push_back(v[b]->ct);
+            ps.push_back(c->cc->MakeCKKSPackedPlaintext(std::vector<double>(weights[b], weights[b] + len), 1,
+                                                        v[0]->ct->GetLevel(), nullptr, slots));
+        }
+        std::vector<std::vector<Ct>> us(ncols);
+        for (size_t k = 0; k < ncols; ++k)
+            for (size_t b = 0; b < nv; ++b) us[k].push_back(u[k * nv + b]->ct);
+        auto got = c->cc->EvalWeightSumMany(vs, ps, us);
         for (size_t k = 0; k < ncols; ++k) outs[k] = wrap(got[k]);
     });
 }

@@ -1825,6 +1825,24 @@ class SfheInternal {
         return buf->ptr;
     }
 
+    // pt over `level`'s local rows (evaluation domain) encoded at `scale`
+    // (EvalWeightSumMany's p: added to a ciphertext whose scale field that
+    // is).  The level's nominal scale is encoded()'s cached encoding; any
+    // other is encoded for this call alone and kept alive by `keep`.
+    static const uint64_t* encodedAtScale(CC* cc, const Plaintext& pt, uint32_t level, double scale,
+                                          std::vector<DeviceBufferPtr>& keep) {
+        SfheContextState* s = cc->st.get();
+        if (scale == s->scale[level]) return encoded(cc, pt, level);
+        std::lock_guard<std::mutex> g(pt->encMutex);
+        const uint32_t ell = s->ellOf(level);
+        if (s->fullScope && s->rows(ell) != ell) SFHE_THROW("internal: encoding scope");
+        auto buf = s->alloc(s->polyWords(level));
+        encodeRows(s, pt, level, buf->ptr, s->qmap(ell), nullptr, scale);
+        sfp_ntt(s->dev, buf->ptr, s->qmap(ell), 0);
+        keep.push_back(buf);
+        return buf->ptr;
+    }
+
     // a canonical ciphertext over existing rows (deferred ops keep the rows
     // they were given pinned, never the caller's possibly reassigned handle)
     static Ct view(CC* cc, const DeviceBufferPtr& buf, uint64_t* c0, uint64_t* c1, uint32_t level, double scale,
@@ -3507,6 +3525,117 @@ std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalGateSumMany(
         auto r = SfheInternal::relinRescale(this, d0[c], d1[c], d2[c], level, slots);
         r->scale = q[0]->scale * u[c][0]->scale / (double)s->primes[ell - 1];
         out[c] = SfheInternal::traced(this, r, "EvalGateSumMany");
+    }
+    return out;
+}
+
+// EvalGateSumMany with the gate p_b + v_b: p_b is encoded at v's scale field,
+// so the gate is an exact sum at Delta_v and every product carries Delta_v
+// Delta_u; the batches' tensors are summed as integers before the column's
+// single relinearisation and rescale.
+std::vector<Ciphertext<DCRTPoly>> CryptoContextImpl<DCRTPoly>::EvalWeightSumMany(
+    const std::vector<Ciphertext<DCRTPoly>>& v, const std::vector<Plaintext>& p,
+    const std::vector<std::vector<Ciphertext<DCRTPoly>>>& u) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    const size_t nb = v.size(), nc = u.size();
+    if (!nb) SFHE_THROW("EvalWeightSumMany: no gates");
+    if (p.size() != nb) SFHE_THROW("EvalWeightSumMany: one weight plaintext per gate is needed");
+    if (nc > kGateMaxColumns)
+        SFHE_THROW("EvalWeightSumMany: " + std::to_string(nc) + " columns (at most " +
+                   std::to_string(kGateMaxColumns) + ")");
+    if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalWeightSumMany");
+    for (const auto& x : v) {
+        if (!x) SFHE_THROW("EvalWeightSumMany: null gate");
+        SfheInternal::deps(s, {&x});
+    }
+    const uint32_t level = v[0]->level, ell = s->ellOf(level);
+    uint32_t slots = v[0]->slots;
+    for (const auto& x : v) {
+        if (x->level != level || x->scale != v[0]->scale)
+            SFHE_THROW("EvalWeightSumMany: the gates must be at one level and one scale");
+        slots = std::max(slots, x->slots);
+    }
+    for (const auto& x : p) {
+        if (!x) SFHE_THROW("EvalWeightSumMany: null weight plaintext");
+        if (x->level > level)
+            SFHE_THROW("EvalWeightSumMany: the weight plaintexts must have at least the gates' limbs (level " +
+                       std::to_string(x->level) + " against the gates' " + std::to_string(level) + ")");
+        slots = std::max(slots, x->slots);
+    }
+    for (const auto& col : u) {
+        if (col.size() != nb) SFHE_THROW("EvalWeightSumMany: every column needs one operand per gate");
+        for (const auto& x : col) {
+            if (!x) SFHE_THROW("EvalWeightSumMany: null operand");
+            SfheInternal::deps(s, {&x});
+            if (x->level > level)
+                SFHE_THROW("EvalWeightSumMany: the operands must have at least the gates' limbs (level " +
+                           std::to_string(x->level) + " against the gates' " + std::to_string(level) + ")");
+            if (x->scale != col[0]->scale) SFHE_THROW("EvalWeightSumMany: a column's operands must be at one scale");
+            slots = std::max(slots, x->slots);
+        }
+    }
+    std::vector<Ciphertext<DCRTPoly>> out(nc);
+    if (!nc) return out;
+    if (ell < 2) SFHE_THROW("no levels left (the weighted sum consumes one level)");
+    // an operand's rows over v's limbs (EvalGateSumMany); p's rows at v's scale
+    std::vector<DeviceBufferPtr> keep;
+    std::vector<const uint64_t*> v0(nb), v1(nb), pr(nb), u0(nc * nb), u1(nc * nb);
+    for (size_t b = 0; b < nb; ++b) {
+        v0[b] = v[b]->c0;
+        v1[b] = v[b]->c1;
+        pr[b] = SfheInternal::encodedAtScale(this, p[b], level, v[0]->scale, keep);
+    }
+    for (size_t c = 0; c < nc; ++c)
+        for (size_t b = 0; b < nb; ++b)
+            std::tie(u0[c * nb + b], u1[c * nb + b]) = SfheInternal::rowsOver(s, u[c][b], ell, keep);
+    const size_t pw = s->polyWords(level);
+    const sfp_limbs m = s->qmap(ell);
+    auto t = s->alloc(3 * pw * nc);
+    std::vector<uint64_t*> d0(nc), d1(nc), d2(nc);
+    for (size_t c = 0; c < nc; ++c) {
+        d0[c] = t->ptr + 3 * pw * c;
+        d1[c] = d0[c] + pw;
+        d2[c] = d1[c] + pw;
+    }
+    const bool fused = sfp_weight_tensor_cols && !SfheInternal::knobOff("SFHE_WINDOW_FUSED") && !s->shardAt(ell) &&
+                       nb <= SFP_WEIGHT_MAX_B &&
+                       sfp_weight_tensor_cols(s->dev, d0.data(), d1.data(), d2.data(), v0.data(), v1.data(), pr.data(),
+                                              u0.data(), u1.data(), (uint32_t)nb, (uint32_t)nc, m) == 0;
+    if (fused) {
+        s->stats.weight_fused++;
+    } else {  // the same integers from the generic prims: a_b0 = v_b0 + p_b, then the tensors summed over b
+        auto a = s->alloc(4 * pw);
+        uint64_t* a0 = a->ptr;
+        uint64_t* t0 = a0 + pw;
+        uint64_t* t1 = t0 + pw;
+        uint64_t* t2 = t1 + pw;
+        for (size_t b = 0; b < nb; ++b) {
+            sfp_add(s->dev, a0, v0[b], pr[b], m);
+            for (size_t c = 0; c < nc; ++c) {
+                if (b == 0) {
+                    sfp_tensor(s->dev, d0[c], d1[c], d2[c], a0, v1[0], u0[c * nb], u1[c * nb], m);
+                    continue;
+                }
+                sfp_tensor(s->dev, t0, t1, t2, a0, v1[b], u0[c * nb + b], u1[c * nb + b], m);
+                sfp_add(s->dev, d0[c], d0[c], t0, m);
+                sfp_add(s->dev, d1[c], d1[c], t1, m);
+                sfp_add(s->dev, d2[c], d2[c], t2, m);
+            }
+        }
+        s->stats.weight_composed++;
+    }
+    s->stats.add += nb;
+    s->stats.tensor += nb * nc;
+    // the fused form, modelled: per tile of CT columns nb (3 + 2 CT) rows read and 3 CT written per limb
+    for (size_t c = 0; c < nc; c += 2) {
+        const double ct = (double)std::min<size_t>(2, nc - c);
+        s->countBytes((nb * (3.0 + 2.0 * ct) + 3.0 * ct) * ell * s->n * 8);
+    }
+    for (size_t c = 0; c < nc; ++c) {
+        auto r = SfheInternal::relinRescale(this, d0[c], d1[c], d2[c], level, slots);
+        r->scale = v[0]->scale * u[c][0]->scale / (double)s->primes[ell - 1];
+        out[c] = SfheInternal::traced(this, r, "EvalWeightSumMany");
     }
     return out;
 }

@@ -426,6 +426,25 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     static constexpr size_t kGateMaxColumns = 8;
     std::vector<Ciphertext<DCRTPoly>> EvalGateSumMany(const std::vector<Ciphertext<DCRTPoly>>& q,
                                                       const std::vector<std::vector<Ciphertext<DCRTPoly>>>& u);
+    // Engine extension (the window sums' weighted column sums):
+    // out[c] = sum_b (p[b] + v[b]) (.) u[c][b], relinearised ONCE per column,
+    // one level below v.  The B gates are a ciphertext v[b] plus a per-slot
+    // plaintext p[b]: the v[b] share one level and one scale, every p[b] is a
+    // plaintext over at least v's limbs and is encoded at v's scale field, so
+    // p + v is exact.  The gates serve all C <= kGateMaxColumns columns;
+    // column c's operands u[c][b] share one scale and have at least v's limbs
+    // (a numerically lower or equal level): they are read over v's limbs.
+    // The result's scale field holds Delta_v Delta_u / q_dropped
+    // (EvalLexStep).  The tensors of all batches and columns are one launch
+    // per tile of two columns where the backend has prims.h
+    // sfp_weight_tensor_cols and B <= SFP_WEIGHT_MAX_B; elsewhere (the C
+    // oracle, SFHE_WINDOW_FUSED=0 -- read per call --, a level whose rows are
+    // dealt over ranks, more batches, or the prim declining) the generic prims
+    // compose the same integers.  OpStats weight_fused / weight_composed count
+    // the calls of each kind.
+    std::vector<Ciphertext<DCRTPoly>> EvalWeightSumMany(const std::vector<Ciphertext<DCRTPoly>>& v,
+                                                        const std::vector<Plaintext>& p,
+                                                        const std::vector<std::vector<Ciphertext<DCRTPoly>>>& u);
     // Engine extension: EvalMult(a_i, b_i) for independent pairs, each formed
     // canonically (rescaled: the values a lazy product takes when its
     // consumer needs the canonical form); pairs at one level run as batched
@@ -804,6 +823,7 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         // and ran as separate products and sums
         uint64_t sumn_batches = 0, sumn_fallbacks = 0;
         uint64_t gate_fused = 0, gate_composed = 0;  // EvalGateSumMany calls: tensors fused / composed of generic prims
+        uint64_t weight_fused = 0, weight_composed = 0;  // EvalWeightSumMany calls likewise
     };
     OpStats GetOpStats() const;
     void ResetOpStats();
@@ -890,7 +910,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 15
+#define SFHE_FACADE_ABI_VERSION 16
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

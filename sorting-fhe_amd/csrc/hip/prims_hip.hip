@@ -2401,6 +2401,87 @@ __global__ __launch_bounds__(kThreads) void k_gate_tensor_cols(const GateArgs<CT
     }
 }
 
+// The window sums' weighted column sums (prims.h sfp_weight_tensor_cols): for a
+// tile of CT columns and nb <= SFP_WEIGHT_MAX_B batches the tensors of
+// (a0, a1)_b = (p_b + v_b0, v_b1) -- v_b a ciphertext, p_b a plaintext row --
+// with (u0, u1)_bc, summed over the batches before any reduction:
+//   d0_c = sum_b a_b0 u_bc0,  d1_c = sum_b (a_b0 u_bc1 + a_b1 u_bc0),  d2_c = sum_b a_b1 u_bc1
+// a_b0 is formed in registers: the canonical residue sfp_add would have stored
+// (one conditional subtraction); each v and p word is read once for the tile's
+// columns.  Each output is ONE reduction of the exact sum of its products: the
+// canonical residue the composed form reaches through sfp_tensor's reduced
+// products and sfp_add.  d1 sums 2 nb products of canonical residues of primes
+// of at most 60 bits, each below 2^120: with nb <= 16 less than 2^125, inside
+// the 128-bit accumulator (the prim declines nb > 16).  The accumulators and
+// the final reductions are k_gate_tensor_cols'; only the gate differs.
+template <int CT>
+struct WeightArgs {
+    const u64* v0[SFP_WEIGHT_MAX_B];
+    const u64* v1[SFP_WEIGHT_MAX_B];
+    const u64* p[SFP_WEIGHT_MAX_B];
+    const u64* u0[CT][SFP_WEIGHT_MAX_B];
+    const u64* u1[CT][SFP_WEIGHT_MAX_B];
+    u64* d0[CT];
+    u64* d1[CT];
+    u64* d2[CT];
+};
+static_assert(SFP_WEIGHT_MAX_B <= 16, "2 * SFP_WEIGHT_MAX_B products below 2^120 must stay inside 128 bits");
+static_assert(sizeof(WeightArgs<2>) == (3 * 2 + 3 * SFP_WEIGHT_MAX_B + 2 * SFP_WEIGHT_MAX_B * 2) * sizeof(void*),
+              "k_weight_tensor_cols takes 3 CT + 3 B + 2 B CT pointers");
+static_assert(sizeof(WeightArgs<2>) + sizeof(sfp_limbs) + 24 <= 4096,
+              "k_weight_tensor_cols' argument block exceeds the 4 KB kernel-argument limit");
+template <int CT>
+__global__ __launch_bounds__(kThreads) void k_weight_tensor_cols(const WeightArgs<CT> A, uint32_t nb, sfp_limbs m,
+                                                                 const sf_barrett* __restrict__ bar, uint32_t logn) {
+    // two coefficients per thread (16-byte loads and stores)
+    const size_t pairs = ((size_t)m.count << logn) >> 1;
+    for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < pairs;
+         i += (size_t)gridDim.x * kThreads) {
+        const uint32_t limb = (uint32_t)((2 * i) >> logn);
+        const sf_barrett B = loadBar(bar, primeOf(m, limb));
+        const u64 q = B.q;
+        Acc s0[CT][2], s1[CT][2], s2[CT][2];
+#pragma unroll
+        for (int c = 0; c < CT; ++c)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) s0[c][h] = s1[c][h] = s2[c][h] = Acc{0, 0};
+        for (uint32_t b = 0; b < nb; ++b) {
+            const ulonglong2 e0 = reinterpret_cast<const ulonglong2*>(A.v0[b])[i];
+            const ulonglong2 a1 = reinterpret_cast<const ulonglong2*>(A.v1[b])[i];
+            const ulonglong2 w = reinterpret_cast<const ulonglong2*>(A.p[b])[i];
+            ulonglong2 a0;
+            a0.x = sf_add(e0.x, w.x, q);
+            a0.y = sf_add(e0.y, w.y, q);
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                const ulonglong2 y0 = reinterpret_cast<const ulonglong2*>(A.u0[c][b])[i];
+                const ulonglong2 y1 = reinterpret_cast<const ulonglong2*>(A.u1[c][b])[i];
+                macc(s0[c][0], a0.x, y0.x);
+                macc(s0[c][1], a0.y, y0.y);
+                macc(s1[c][0], a0.x, y1.x);  // d1: 2 nb products, < 2^125
+                macc(s1[c][0], a1.x, y0.x);
+                macc(s1[c][1], a0.y, y1.y);
+                macc(s1[c][1], a1.y, y0.y);
+                macc(s2[c][0], a1.x, y1.x);
+                macc(s2[c][1], a1.y, y1.y);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            ulonglong2 r0, r1, r2;
+            r0.x = sf_reduce128_acc(s0[c][0].lo, s0[c][0].hi, &B);
+            r0.y = sf_reduce128_acc(s0[c][1].lo, s0[c][1].hi, &B);
+            r1.x = sf_reduce128_acc(s1[c][0].lo, s1[c][0].hi, &B);
+            r1.y = sf_reduce128_acc(s1[c][1].lo, s1[c][1].hi, &B);
+            r2.x = sf_reduce128_acc(s2[c][0].lo, s2[c][0].hi, &B);
+            r2.y = sf_reduce128_acc(s2[c][1].lo, s2[c][1].hi, &B);
+            reinterpret_cast<ulonglong2*>(A.d0[c])[i] = r0;
+            reinterpret_cast<ulonglong2*>(A.d1[c])[i] = r1;
+            reinterpret_cast<ulonglong2*>(A.d2[c])[i] = r2;
+        }
+    }
+}
+
 struct PtrList {
     const u64* p[SFP_MAX_WSUM];
 };
@@ -6051,6 +6132,72 @@ int sfp_gate_tensor_cols(sfp_dev* d, uint64_t* const* d0, uint64_t* const* d1, u
     uint32_t c = 0;
     for (; c + 2 <= nc; c += 2) gateTile<2>(d, d0, d1, d2, q0, q1, u0, u1, ka, nb, c, m, words);
     if (c < nc) gateTile<1>(d, d0, d1, d2, q0, q1, u0, u1, ka, nb, c, m, words);
+    return 0;
+}
+
+template <int CT>
+static void weightTile(sfp_dev* d, uint64_t* const* d0, uint64_t* const* d1, uint64_t* const* d2,
+                       const uint64_t* const* v0, const uint64_t* const* v1, const uint64_t* const* p,
+                       const uint64_t* const* u0, const uint64_t* const* u1, uint32_t nb, uint32_t c0, sfp_limbs m,
+                       size_t words) {
+    WeightArgs<CT> A;
+    std::memset(&A, 0, sizeof A);
+    for (uint32_t b = 0; b < nb; ++b) {
+        A.v0[b] = v0[b];
+        A.v1[b] = v1[b];
+        A.p[b] = p[b];
+    }
+    for (int c = 0; c < CT; ++c) {
+        for (uint32_t b = 0; b < nb; ++b) {
+            A.u0[c][b] = u0[(size_t)(c0 + c) * nb + b];
+            A.u1[c][b] = u1[(size_t)(c0 + c) * nb + b];
+        }
+        A.d0[c] = d0[c0 + c];
+        A.d1[c] = d1[c0 + c];
+        A.d2[c] = d2[c0 + c];
+    }
+    SFP_GO(k_weight_tensor_cols<CT>, dim3(ewGrid(words / 2)), dim3(kThreads), A, nb, m, d->bar, d->logn);
+    checkLaunch(d, "weight_tensor_cols");
+}
+
+int sfp_weight_tensor_cols(sfp_dev* d, uint64_t* const* d0, uint64_t* const* d1, uint64_t* const* d2,
+                           const uint64_t* const* v0, const uint64_t* const* v1, const uint64_t* const* p,
+                           const uint64_t* const* u0, const uint64_t* const* u1, uint32_t nb, uint32_t nc,
+                           sfp_limbs m) {
+    // every pointer rides in the kernels' argument blocks (no upload, no ring
+    // slot: capturable, any lane); 16-byte accesses need aligned rows.  All
+    // the checks come before the first launch: a decline writes nothing.
+    if (!nb || nb > SFP_WEIGHT_MAX_B || !nc || nc > SFP_WEIGHT_MAX_C) return -1;
+    if (!m.count || m.count > SFP_MAX_LIMBS || d->n < 2) return -1;
+    const size_t words = (size_t)m.count * d->n;
+    const uintptr_t bytes = words * 8;
+    std::vector<uintptr_t> outs, ins;
+    for (uint32_t c = 0; c < nc; ++c)
+        for (uint64_t* const* o : {d0, d1, d2}) outs.push_back((uintptr_t)o[c]);
+    for (uint32_t b = 0; b < nb; ++b) {
+        ins.push_back((uintptr_t)v0[b]);
+        ins.push_back((uintptr_t)v1[b]);
+        ins.push_back((uintptr_t)p[b]);
+    }
+    for (size_t k = 0; k < (size_t)nc * nb; ++k) {
+        ins.push_back((uintptr_t)u0[k]);
+        ins.push_back((uintptr_t)u1[k]);
+    }
+    for (uintptr_t in : ins)
+        if (!in || (in & 15)) return -1;
+    for (size_t k = 0; k < outs.size(); ++k) {
+        const uintptr_t o = outs[k];
+        if (!o || (o & 15)) return -1;
+        for (uintptr_t in : ins)
+            if (o < in + bytes && in < o + bytes) return -1;
+        for (size_t j = 0; j < k; ++j)
+            if (o < outs[j] + bytes && outs[j] < o + bytes) return -1;
+    }
+    if (!limbsOk(d, m, "weight_tensor_cols")) return -1;
+    // tiles of two columns, then a remainder of one
+    uint32_t c = 0;
+    for (; c + 2 <= nc; c += 2) weightTile<2>(d, d0, d1, d2, v0, v1, p, u0, u1, nb, c, m, words);
+    if (c < nc) weightTile<1>(d, d0, d1, d2, v0, v1, p, u0, u1, nb, c, m, words);
     return 0;
 }
 

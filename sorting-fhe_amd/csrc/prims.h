@@ -464,6 +464,34 @@ SFP_OPTIONAL int sfp_gate_tensor_cols(sfp_dev* d, uint64_t* const* d0, uint64_t*
                                       const uint64_t* const* u0, const uint64_t* const* u1, const uint64_t* kr,
                                       uint32_t nb, uint32_t nc, sfp_limbs m);
 
+// ---- optional: the window sums' weighted column sums (SUM OVER an ordered frame) --
+// nb gates p_b + v_b -- v_b a ciphertext (v0[b], v1[b]), p_b a plaintext row
+// p[b] -- shared by nc columns, column c's operand of batch b the ciphertext
+// u0[c * nb + b], u1[c * nb + b]; with (a0, a1)_b = (p_b + v_b0 mod q, v_b1),
+// a_b0 the canonical residue sfp_add stores, all m.count rows in the evaluation
+// domain:
+//   d0[c] = sum_b a_b0 u_bc0,  d1[c] = sum_b (a_b0 u_bc1 + a_b1 u_bc0),  d2[c] = sum_b a_b1 u_bc1
+// i.e. sum_b (p_b + v_b) (.) u_bc before its ONE relinearisation per column.
+// Issued as tiles of two columns and a remainder of one (kernel
+// k_weight_tensor_cols<CT>): a tile reads each v and p word once for its
+// columns.  The canonical residues of, per batch, sfp_add (v_b0, p_b), per
+// (b, c) sfp_tensor(a_b, u_bc), and three sfp_add from the second batch on.
+// Each output is one reduction of the exact sum of its products: d1 sums 2 nb
+// products of canonical residues of primes of at most 60 bits, below 2^125 for
+// nb <= SFP_WEIGHT_MAX_B = 16.  Every pointer travels in the kernels'
+// arguments: no upload and no host synchronisation, so the prim may be
+// captured and issued on any lane.  Weak like the prims above: where its
+// address is null (the C oracle), or it returns -1 with nothing written (nb = 0
+// or nb > SFP_WEIGHT_MAX_B, nc = 0 or nc > SFP_WEIGHT_MAX_C, more than
+// SFP_MAX_LIMBS rows, a row not 16-byte aligned, an output overlapping an
+// input or another output), the host layer runs the generic prims.
+#define SFP_WEIGHT_MAX_B 16
+#define SFP_WEIGHT_MAX_C 8
+SFP_OPTIONAL int sfp_weight_tensor_cols(sfp_dev* d, uint64_t* const* d0, uint64_t* const* d1, uint64_t* const* d2,
+                                        const uint64_t* const* v0, const uint64_t* const* v1,
+                                        const uint64_t* const* p, const uint64_t* const* u0,
+                                        const uint64_t* const* u1, uint32_t nb, uint32_t nc, sfp_limbs m);
+
 // ---- optional: the giant-step sums of several columns under one plaintext set ----
 // nc columns (records' payloads placed by one rank) share the ng x nin
 // plaintexts b[g * nin + j] of sfp_mac_plain2_multi; column c has its own

@@ -60,10 +60,12 @@ ABI_SYMBOLS = [
     "sfhe_eval_mult_sum", "sfhe_sumn_counts",
     "sfhe_eval_mult_sum_many", "sfhe_sumn_batch_counts", "sfhe_ct_relabel_scale",
     "sfhe_group_params", "sfhe_sorter_group", "sfhe_eval_gate_sum_many", "sfhe_group_counts",
+    "sfhe_window_params", "sfhe_sorter_window", "sfhe_eval_weight_sum_many", "sfhe_window_counts",
 ]
 
 MAX_COLUMNS = 8  # SFHE_MAX_COLUMNS
 LEX_KEYS = 4  # SFHE_LEX_KEYS
+FRAMES = {"rows": 0, "range": 1, "below": 2}  # SFHE_FRAME_*
 
 
 class SfheError(RuntimeError):
@@ -224,6 +226,10 @@ _SIGS = {
     "sfhe_sorter_group": (C.c_int, [_VP, _VP, _PVP, _SZ, C.c_int, C.c_int, C.c_int, C.c_int, _PVP, _PVP, _PVP]),
     "sfhe_eval_gate_sum_many": (C.c_int, [_VP, _PVP, _SZ, _PVP, _SZ, _PVP]),
     "sfhe_group_counts": (C.c_int, [_VP, _PU64, _PU64]),
+    "sfhe_window_params": (C.c_int, [_U32, _PU32, _PI32, _SZ, _PSZ]),
+    "sfhe_sorter_window": (C.c_int, [_VP, _VP, _PVP, _SZ, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PVP, _PVP]),
+    "sfhe_eval_weight_sum_many": (C.c_int, [_VP, _PVP, _SZ, C.POINTER(_PD), _SZ, _U32, _PVP, _SZ, _PVP]),
+    "sfhe_window_counts": (C.c_int, [_VP, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -614,6 +620,37 @@ class Engine:
         self._chk(self.lib.sfhe_group_counts(self.ctx, C.byref(f), C.byref(c)))
         return f.value, c.value
 
+    def weight_sum_many(self, vs, weights, us, slots: int = 0):
+        """[sum_b (weights[b] + vs[b]) * us[c][b] for each column c], one level below the gates
+        (one relinearisation and one rescale per column): the window sums' weighted column sums.
+        weights[b] is a vector of slot values, encoded at vs' scale; the gates share one level;
+        operands may sit at a numerically lower level."""
+        vs, us = list(vs), [list(col) for col in us]
+        weights = [[float(x) for x in w] for w in weights]
+        if len(weights) != len(vs):
+            raise SfheError("sfhe error -1: one weight vector per gate is needed")
+        if len({len(w) for w in weights}) > 1:
+            raise SfheError("sfhe error -1: the weight vectors must have one length")
+        for col in us:
+            if len(col) != len(vs):
+                raise SfheError("sfhe error -1: every column needs one operand per gate")
+        vh = (_VP * max(len(vs), 1))(*[v.h if v is not None else None for v in vs])
+        rows = [_darr(w) for w in weights]
+        wh = (_PD * max(len(rows), 1))(*[C.cast(r, _PD) for r in rows])
+        flat = [x.h if x is not None else None for col in us for x in col]
+        uh = (_VP * max(len(flat), 1))(*flat)
+        outs = (_VP * max(len(us), 1))()
+        self._chk(self.lib.sfhe_eval_weight_sum_many(self.ctx, vh, len(vs), wh, len(weights[0]) if weights else 0,
+                                                     slots, uh, len(us), outs))
+        return [Ct(self, C.c_void_p(outs[i])) for i in range(len(us))]
+
+    def window_counts(self):
+        """(fused, composed) weight_sum_many calls (Sorter.window's included) since the last
+        op_stats reset."""
+        f, c = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_window_counts(self.ctx, C.byref(f), C.byref(c)))
+        return f.value, c.value
+
     def lex_counts(self):
         """(fused, composed) lex_step tensors (rank_lex's included) since the last op_stats reset."""
         f, c = C.c_uint64(), C.c_uint64()
@@ -949,6 +986,27 @@ class Sorter:
         return {"count": Ct(self.eng, cnt), "index": Ct(self.eng, idx) if index else None,
                 "sums": [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cts))]}
 
+    # -- aggregates OVER (ORDER BY key) --
+    def window(self, keys: Ct, cts=(), frame: str = "rows", count: bool = False, n: int = 3, dg: int = 2,
+               df: int = 2):
+        """SUM(col) OVER (ORDER BY key) and the counts that go with it, in input order:
+        {"count": slot r = rows in row r's frame (None unless count=True), "sums": [slot r =
+        column's sum over row r's frame]}.  Row j is in row r's frame where (key_j, j) <=
+        (key_r, r) ("rows": running totals in stable order; count = ROW_NUMBER()), key_j <= key_r
+        ("range": SQL's default frame; count = N * CUME_DIST()) or key_j < key_r ("below"; count =
+        RANK() - 1).  The context needs window_params' depth for the sign configuration
+        (SfheError otherwise); no placement is evaluated.  Payload values lie in [-1, 1]."""
+        if frame not in FRAMES:
+            raise SfheError(f"sfhe error -1: unknown frame {frame!r} (one of {', '.join(FRAMES)})")
+        cts = list(cts)
+        cs = (_VP * max(len(cts), 1))(*[c.h if c is not None else None for c in cts])
+        cnt = _VP()
+        outs = (_VP * max(len(cts), 1))()
+        self.eng._chk(self.eng.lib.sfhe_sorter_window(self.h, keys.h, cs, len(cts), FRAMES[frame], int(bool(count)),
+                                                      n, dg, df, C.byref(cnt), outs))
+        return {"count": Ct(self.eng, cnt) if count else None,
+                "sums": [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cts))]}
+
     def top_k(self, ct: Ct, k: int, largest: bool = False, **kw) -> Ct:
         """The k smallest values in ascending order (largest: the k largest, descending)."""
         return self.select(ct, [self.N - 1 - i for i in range(k)] if largest else list(range(k)), **kw)
@@ -1039,6 +1097,20 @@ def group_params(N: int, backend: str = "hip"):
         raise SfheError(lib.sfhe_last_error().decode())
     buf = (C.c_int32 * cnt.value)()
     lib.sfhe_group_params(N, None, buf, cnt.value, None)
+    return depth.value, list(buf)
+
+
+def window_params(N: int, backend: str = "hip"):
+    """(depth, rotations) for Sorter.window with N's default sign configuration: the stable
+    rank's depth plus one (no placement) and the rank's rotation amounts."""
+    lib = load(backend)
+    depth = C.c_uint32()
+    cnt = C.c_size_t()
+    rc = lib.sfhe_window_params(N, C.byref(depth), None, 0, C.byref(cnt))
+    if rc != SFHE_OK:
+        raise SfheError(lib.sfhe_last_error().decode())
+    buf = (C.c_int32 * cnt.value)()
+    lib.sfhe_window_params(N, None, buf, cnt.value, None)
     return depth.value, list(buf)
 
 
