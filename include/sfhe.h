@@ -44,7 +44,9 @@ extern "C" {
  * sfhe_sumn_batch_counts, sfhe_ct_relabel_scale, and the grouping by a key:
  * sfhe_group_params, sfhe_sorter_group, sfhe_eval_gate_sum_many,
  * sfhe_group_counts, and the window sums: SFHE_FRAME_*, sfhe_window_params,
- * sfhe_sorter_window, sfhe_eval_weight_sum_many, sfhe_window_counts) */
+ * sfhe_sorter_window, sfhe_eval_weight_sum_many, sfhe_window_counts, and the
+ * join of two tables: sfhe_join_params, sfhe_sorter_join, sfhe_eval_gate_or,
+ * sfhe_join_counts) */
 
 #define SFHE_OK 0
 #define SFHE_EINVAL (-1)   /* bad argument */
@@ -517,6 +519,42 @@ int sfhe_sorter_window(sfhe_sorter* s, const sfhe_ct* keys, const sfhe_ct* const
 int sfhe_eval_weight_sum_many(sfhe_ctx* c, const sfhe_ct* const* v, size_t nv, const double* const* weights,
                               size_t len, uint32_t slots, const sfhe_ct* const* u, size_t ncols, sfhe_ct** outs);
 int sfhe_window_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
+/* Engine extensions (additions at ABI 3): the join of two encrypted tables on
+ * 1 <= nkeys <= 4 keys -- SELECT a.*, COUNT(b.*), SUM(b.col) FROM a LEFT JOIN b
+ * ON a.k1 = b.k1 [AND a.k2 = b.k2 ...] -- every result in table A's input order.
+ * keys_a[k], keys_b[k] and the 0 <= ncols <= SFHE_MAX_COLUMNS columns of table B
+ * sit at one level and slot count.  *count: slot r holds the number of rows of B
+ * that agree with A's row r on every key.  sums_out[c]: slot r holds the sum of
+ * cols_b[c] over those rows.  *count is one level above the sums, which end at
+ * the context's sfhe_join_params depth: the grouping's plus ceil(log2 nkeys).
+ * Preconditions: per key, any A value and any B value are equal or at least the
+ * sign configuration's resolution apart (1/N for the defaults) and their
+ * difference lies in the sign's domain (the keys are in the sort's input
+ * range); both tables occupy N rows: a shorter B is padded with a key no A row
+ * takes, A's padded rows are ignored by the client.  With unique B keys *count
+ * is the 0/1 semi-join flag (1 - *count the anti-join flag) and a sum is the
+ * looked-up value; a table joined with itself is GROUP BY k1, ..., km.
+ * sfhe_join_params: the mult_depth of sfhe_sorter_join on nkeys keys with N's
+ * default sign configuration and the rotation amounts it uses
+ * (sfhe_group_params': the rank's).  cap / count as sfhe_direct_sort_params.
+ * A key or column count out of range, a NULL entry or inputs at different
+ * levels or slot counts: SFHE_EINVAL; too little depth: SFHE_ESCHEME, the
+ * message naming the depth needed, before anything is computed.  Always eager. */
+int sfhe_join_params(uint32_t N, uint32_t nkeys, uint32_t* mult_depth, int32_t* rotations, size_t cap,
+                     size_t* count);
+int sfhe_sorter_join(sfhe_sorter* s, const sfhe_ct* const* keys_a, const sfhe_ct* const* keys_b, size_t nkeys,
+                     const sfhe_ct* const* cols_b, size_t ncols, int n, int dg, int df, sfhe_ct** count,
+                     sfhe_ct** sums_out);
+/* *out = a + b - a (.) b (the OR of two 0/1 gates), relinearised once, one level
+ * below the lower operand; the operands keep their own scales and may sit at
+ * different levels (the one with more limbs is read over the other's).  A NULL
+ * argument or different slot counts: SFHE_EINVAL.
+ * sfhe_join_counts: such calls whose tensor ran as the one fused launch
+ * (sfp_or_tensor) and as the composed generic prims since the last sfhe_op_stats
+ * reset (SFHE_JOIN_FUSED=0, read per call, composes; the results are
+ * bit-identical). */
+int sfhe_eval_gate_or(sfhe_ctx* c, const sfhe_ct* a, const sfhe_ct* b, sfhe_ct** out);
+int sfhe_join_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed);
 /* nodes of the captured record sort (0 while none); sfhe_sorter_graph_nodes
  * keeps reporting the plain / stable sort's graph */
 int sfhe_sorter_records_graph_nodes(const sfhe_sorter* s, uint64_t* nodes);

@@ -30,6 +30,9 @@
 // key's group, its number inside the group and the group's column sums.
 // Window sums: windowSums gives every row, in input order, the
 // running count and column sums over the rows before it in key order.
+// Join: joinAggregate gives every row of a table A the number
+// of rows of a table B that agree with it on up to SFHE_LEX_KEYS keys, and B's
+// column sums over them.
 // What these methods share is written once: runBatches (the batches over
 // lanes and batch groups), sumOverPartitions (batch sum and folds),
 // sfhe::SincIndicator (the placements' and selections' indicator), MemoTag and
@@ -45,6 +48,7 @@
 
 #include <algorithm>
 #include <exception>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <map>
@@ -140,6 +144,13 @@ inline int groupDepth(const CompositeSignConfig& c) { return stableRankDepth(c);
 // Window sums over an ordered frame: the stable rank's tie
 // term as the gate, then 1 (the gated product); no placement.
 inline int windowDepth(const CompositeSignConfig& c) { return stableRankDepth(c) + 1; }
+// Join of two tables on m keys: the grouping's levels, and
+// the balanced tree of EvalGateOr over the keys' gates (one level per layer).
+inline int joinDepth(const CompositeSignConfig& c, int m) {
+    int layers = 0;
+    while ((1 << layers) < m) ++layers;
+    return groupDepth(c) + layers;
+}
 
 // getSizeParameters' (depth, rotation keys) for N (reference :87-201);
 // nullptr when the reference has no entry.
@@ -961,6 +972,110 @@ class DirectSort : public SortBase<N> {
             out.count = m_cc->EvalAdd(acc, K);
         }
         ph.mark("window: count");
+        return out;
+    }
+
+    // ---- join of two tables on up to SFHE_LEX_KEYS keys (SELECT a.*, COUNT(b.*),
+    // SUM(b.col) FROM a LEFT JOIN b ON a.k1 = b.k1 AND ...) ----
+    struct JoinResult {
+        Ciphertext<DCRTPoly> count;              // count_r = #{j : keyB_kj = keyA_kr for every k}
+        std::vector<Ciphertext<DCRTPoly>> sums;  // sums[c]_r = sum of colsB[c]_j over those j
+    };
+    // Every result is in table A's input order.  In groupAggregate's slot
+    // layout (slot pN + r of batch b pairs A's row r with B's row j = (r + d)
+    // mod N, d = bP + p; no self offset), with s_kb the composite sign of
+    // keyA_kr - keyB_kj, q_kb = s_kb^2 ("key k differs"), Q_b = q_1b v ... v q_mb
+    // ("some key differs": a balanced tree of m - 1 EvalGateOr, (q1 v q2) v q3
+    // for m = 3) and u_bc column c of B at row j in the same layout:
+    //   count_r  = N - fold(sum_b Q_b)_r                    at Q's level
+    //   sum_cr   = fold(sum_b (1 - Q_b) (.) u_bc)_r          one level below Q
+    // The flow is groupAggregate's: the baby rotations of B's keys and columns
+    // (table A needs no rotation: its keys are only widened to S slots), each
+    // batch on its lane, after the join ONE EvalGateSumMany for all batches and
+    // columns, the sum of the Q_b and the rank's doubling folds.  With m = 1
+    // and keysA[0], keysB[0] one ciphertext the op sequence is groupAggregate's
+    // without the index.  Depth joinDepth: the grouping's plus ceil(log2 m);
+    // the count ends one level above the sums.  Eager (no graph).
+    // Preconditions: per key, any A value and any B value are equal or at
+    // least the sign configuration's resolution apart, and their difference is
+    // in the sign's domain (the keys are in the sort's input range); both
+    // tables occupy N rows (a shorter B is padded with a key no A row takes,
+    // A's padded rows are ignored by the client).
+    // With unique B keys the count is the 0/1 semi-join flag (1 - count the
+    // anti-join flag) and a sum is the looked-up value; a table joined with
+    // itself on m keys is GROUP BY k1, ..., km.
+    JoinResult joinAggregate(const std::vector<Ciphertext<DCRTPoly>>& keysA,
+                             const std::vector<Ciphertext<DCRTPoly>>& keysB,
+                             const std::vector<Ciphertext<DCRTPoly>>& colsB, SignFunc SignFunc, SignConfig& Cfg,
+                             size_t maxCols) {
+        const size_t m = keysA.size(), C = colsB.size();
+        if (m < 1 || m > SFHE_LEX_KEYS)
+            throw std::invalid_argument("join: " + std::to_string(m) + " keys (1 .. " +
+                                        std::to_string(SFHE_LEX_KEYS) + ")");
+        if (keysB.size() != m)
+            throw std::invalid_argument("join: " + std::to_string(m) + " keys of table A against " +
+                                        std::to_string(keysB.size()) + " of table B");
+        if (C > maxCols)
+            throw std::invalid_argument("join: " + std::to_string(C) + " payload columns (at most " +
+                                        std::to_string(maxCols) + ")");
+        const auto& k0 = keysA[0];
+        for (const auto* list : {&keysA, &keysB, &colsB})
+            for (const auto& c : *list)
+                if (c->GetLevel() != k0->GetLevel() || c->GetSlots() != k0->GetSlots())
+                    throw std::invalid_argument("join: the keys and the columns must be at one level and slot count");
+        const int need = (int)k0->GetLevel() + sfhe::joinDepth(Cfg.compos, (int)m);
+        if ((int)m_cc->GetMultiplicativeDepth() < need)
+            throw OpenFHEException("join: needs multiplicative depth " + std::to_string(need) +
+                                   " (the grouping's and one level per layer of the keys' OR tree); the context has " +
+                                   std::to_string(m_cc->GetMultiplicativeDepth()));
+        const sfhe::RankLayout L(N, max_batch);
+        sfhe::PhaseTimer ph(m_cc);
+        std::vector<std::vector<Ciphertext<DCRTPoly>>> pre(m), preCols(C);
+        for (size_t k = 0; k < m; ++k) pre[k] = rankBabyRotations(keysB[k], L);
+        for (size_t c = 0; c < C; ++c) preCols[c] = rankBabyRotations(colsB[c], L);
+        ph.mark("join: baby rotations");
+
+        // Q over q[lo, hi): the halves' ORs, the first half taking the odd key
+        std::function<Ciphertext<DCRTPoly>(const std::vector<Ciphertext<DCRTPoly>>&, size_t, size_t)> orTree =
+            [&](const std::vector<Ciphertext<DCRTPoly>>& q, size_t lo, size_t hi) {
+                if (hi - lo == 1) return q[lo];
+                const size_t mid = lo + (hi - lo + 1) / 2;
+                return m_cc->EvalGateOr(orTree(q, lo, mid), orTree(q, mid, hi));
+            };
+        std::vector<Ciphertext<DCRTPoly>> Q(L.B);
+        std::vector<std::vector<Ciphertext<DCRTPoly>>> u(C, std::vector<Ciphertext<DCRTPoly>>(L.B));
+        const auto split = runBatches(L.B, [&](int b) {
+            std::vector<Ciphertext<DCRTPoly>> shifted(m), q(m);
+            for (size_t k = 0; k < m; ++k) shifted[k] = vecRotsOpt(pre[k], L.P, L.S, L.npRank, b);
+            for (size_t c = 0; c < C; ++c) u[c][b] = vecRotsOpt(preCols[c], L.P, L.S, L.npRank, b);
+            ph.mark("  join batch: vecRotsOpt");
+            for (size_t k = 0; k < m; ++k) {
+                auto dup = keysA[k]->Clone();
+                dup->SetSlots(L.S);
+                auto s = sign(m_cc->EvalSub(dup, shifted[k]), m_cc, SignFunc, Cfg);
+                q[k] = m_cc->EvalMult(s, s);
+            }
+            Q[b] = orTree(q, 0, m);
+            ph.mark("  join batch: signs + gate");
+        });
+        split.gatherParts(m_cc, Q);
+        for (auto& col : u) split.gatherParts(m_cc, col);
+        ph.mark("join: batches");
+
+        auto fold = [&](Ciphertext<DCRTPoly> x) {
+            x->SetSlots(L.S);
+            return sumOverPartitions(x, {}, L.S);
+        };
+        JoinResult out;
+        if (C) {
+            out.sums = m_cc->EvalGateSumMany(Q, u);
+            for (auto& x : out.sums) x = fold(x);
+        }
+        ph.mark("join: gated sums + folds");
+        auto acc = Q[0]->Clone();
+        for (int b = 1; b < L.B; ++b) m_cc->EvalAddInPlace(acc, Q[b]);
+        out.count = m_cc->EvalSub((double)N, fold(acc));
+        ph.mark("join: count");
         return out;
     }
 

@@ -119,6 +119,9 @@ struct SorterBase {
     // {count, index (null unless asked for), sums...}
     virtual std::vector<Ct> group(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, bool wantIndex) = 0;
     // {count (null unless asked for), sums...}
+    // {count, sums...}
+    virtual std::vector<Ct> join(const std::vector<Ct>& keysA, const std::vector<Ct>& keysB,
+                                 const std::vector<Ct>& colsB, SignConfig& cfg) = 0;
     virtual std::vector<Ct> window(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, int frame,
                                    bool wantCount) = 0;
     virtual Ct hybrid1(const Ct& in, SignConfig& cfg, const PrivateKey<DCRTPoly>& sk) = 0;
@@ -190,6 +193,13 @@ struct Sorter : SorterBase {
     std::vector<Ct> group(const Ct& keys, const std::vector<Ct>& cols, SignConfig& cfg, bool wantIndex) override {
         auto r = ds.groupAggregate(keys, cols, SignFunc::CompositeSign, cfg, wantIndex, SFHE_MAX_COLUMNS);
         std::vector<Ct> out{r.count, r.index};
+        out.insert(out.end(), r.sums.begin(), r.sums.end());
+        return out;
+    }
+    std::vector<Ct> join(const std::vector<Ct>& keysA, const std::vector<Ct>& keysB, const std::vector<Ct>& colsB,
+                         SignConfig& cfg) override {
+        auto r = ds.joinAggregate(keysA, keysB, colsB, SignFunc::CompositeSign, cfg, SFHE_MAX_COLUMNS);
+        std::vector<Ct> out{r.count};
         out.insert(out.end(), r.sums.begin(), r.sums.end());
         return out;
     }
@@ -486,6 +496,14 @@ int sfhe_window_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
     auto s = c->cc->GetOpStats();
     *fused = s.weight_fused;
     *composed = s.weight_composed;
+    return SFHE_OK;
+}
+
+int sfhe_join_counts(sfhe_ctx* c, uint64_t* fused, uint64_t* composed) {
+    REQUIRE(c && fused && composed, "null argument");
+    auto s = c->cc->GetOpStats();
+    *fused = s.or_fused;
+    *composed = s.or_composed;
     return SFHE_OK;
 }
 
@@ -1138,6 +1156,49 @@ int sfhe_eval_weight_sum_many(sfhe_ctx* c, const sfhe_ct* const* v, size_t nv, c
         auto got = c->cc->EvalWeightSumMany(vs, ps, us);
         for (size_t k = 0; k < ncols; ++k) outs[k] = wrap(got[k]);
     });
+}
+
+int sfhe_join_params(uint32_t N, uint32_t nkeys, uint32_t* mult_depth, int32_t* rot, size_t cap, size_t* count) {
+    REQUIRE(validN(N), "N must be a power of two in [4, 1024]");
+    REQUIRE(nkeys >= 1 && nkeys <= SFHE_LEX_KEYS, "key count out of range (1 .. 4)");
+    return guard([&] {
+        const std::set<int> r = rankRotations(N);
+        if (mult_depth) *mult_depth = (uint32_t)sfhe::joinDepth(sfhe::defaultSignConfig((int)N), (int)nkeys);
+        if (count) *count = r.size();
+        size_t i = 0;
+        for (int v : r) {
+            if (i >= cap || !rot) break;
+            rot[i++] = v;
+        }
+    });
+}
+
+int sfhe_sorter_join(sfhe_sorter* s, const sfhe_ct* const* keys_a, const sfhe_ct* const* keys_b, size_t nkeys,
+                     const sfhe_ct* const* cols_b, size_t ncols, int n, int dg, int df, sfhe_ct** count,
+                     sfhe_ct** sums_out) {
+    REQUIRE(s && keys_a && keys_b && count && (ncols == 0 || (cols_b && sums_out)), "null argument");
+    REQUIRE(nkeys >= 1 && nkeys <= SFHE_LEX_KEYS, "key count out of range (1 .. 4)");
+    REQUIRE(ncols <= SFHE_MAX_COLUMNS, "column count out of range (0 .. SFHE_MAX_COLUMNS)");
+    for (size_t k = 0; k < nkeys; ++k) REQUIRE(keys_a[k] && keys_b[k], "null key");
+    for (size_t i = 0; i < ncols; ++i) REQUIRE(cols_b[i], "null column");
+    return guard([&] {
+        auto cfg = cfgOf(n, dg, df);
+        std::vector<Ct> ka, kb, in;
+        for (size_t k = 0; k < nkeys; ++k) {
+            ka.push_back(keys_a[k]->ct);
+            kb.push_back(keys_b[k]->ct);
+        }
+        for (size_t i = 0; i < ncols; ++i) in.push_back(cols_b[i]->ct);
+        auto got = s->impl->join(ka, kb, in, cfg);
+        *count = wrap(got[0]);
+        for (size_t i = 0; i < ncols; ++i) sums_out[i] = wrap(got[1 + i]);
+    });
+}
+
+int sfhe_eval_gate_or(sfhe_ctx* c, const sfhe_ct* a, const sfhe_ct* b, sfhe_ct** out) {
+    REQUIRE(c && a && b && out, "null argument");
+    REQUIRE(a->ct->GetSlots() == b->ct->GetSlots(), "the operands must have one slot count");
+    return guard([&] { *out = wrap(c->cc->EvalGateOr(a->ct, b->ct)); });
 }
 
 int sfhe_sorter_sort_hybrid1(sfhe_sorter* s, sfhe_ct* in, int n, int dg, int df, sfhe_ct** out) {

@@ -3421,6 +3421,63 @@ Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalLexStep(const Ciphertext<D
     return SfheInternal::traced(this, r, "EvalLexStep");
 }
 
+// One tensor at the lower operand's level: kb a and ka b carry Delta_a Delta_b
+// as the product -a (.) b does (ka, kb the residues of the operands' scales,
+// formed as EvalLexStep's kr), so the sum is exact.  One relinearisation, one
+// rescale; the result's scale field is Delta_a Delta_b / q_dropped.
+Ciphertext<DCRTPoly> CryptoContextImpl<DCRTPoly>::EvalGateOr(const Ciphertext<DCRTPoly>& a,
+                                                            const Ciphertext<DCRTPoly>& b) {
+    OpLock g(st.get());
+    SfheContextState* s = st.get();
+    if (!a || !b) SFHE_THROW("EvalGateOr: null operand");
+    SfheInternal::deps(s, {&a, &b});
+    if (a->slots != b->slots)
+        SFHE_THROW("EvalGateOr: the operands must have one slot count (" + std::to_string(a->slots) + " against " +
+                   std::to_string(b->slots) + ")");
+    if (!s->relinKey) SFHE_THROW("EvalMultKeyGen must be called before EvalGateOr");
+    const uint32_t level = std::max(a->level, b->level), ell = s->ellOf(level);
+    if (ell < 2) SFHE_THROW("no levels left (the OR of two gates consumes one level)");
+    // the operand with more limbs over the other's: a prefix of its own rows,
+    // gathered where they are dealt over the ranks and this level is replicated
+    std::vector<DeviceBufferPtr> keep;
+    const auto [a0, a1] = SfheInternal::rowsOver(s, a, ell, keep);
+    const auto [b0, b1] = SfheInternal::rowsOver(s, b, ell, keep);
+    const auto ka = SfheInternal::constResidues(s, a->scale, ell);
+    const auto kb = SfheInternal::constResidues(s, b->scale, ell);
+    const size_t pw = s->polyWords(level);
+    const sfp_limbs m = s->qmap(ell);
+    const auto [d0, d1, d2, t] = SfheInternal::alloc3(s, pw);
+    const bool fused = sfp_or_tensor && !SfheInternal::knobOff("SFHE_JOIN_FUSED") && !s->shardAt(ell) &&
+                       sfp_or_tensor(s->dev, d0, d1, d2, a0, a1, b0, b1, ka.data(), kb.data(), m) == 0;
+    if (fused) {
+        s->stats.or_fused++;
+    } else {  // the same integers from the generic prims: na = -a, the tensor of na and b, then + kb a + ka b
+        auto w = s->alloc(4 * pw);
+        uint64_t* n0 = w->ptr;
+        uint64_t* n1 = n0 + pw;
+        uint64_t* l0 = n1 + pw;
+        uint64_t* l1 = l0 + pw;
+        sfp_neg(s->dev, n0, a0, m);
+        sfp_neg(s->dev, n1, a1, m);
+        sfp_tensor(s->dev, d0, d1, d2, n0, n1, b0, b1, m);
+        sfp_mul_const(s->dev, l0, a0, kb.data(), m);
+        sfp_mul_const(s->dev, l1, a1, kb.data(), m);
+        sfp_add(s->dev, d0, d0, l0, m);
+        sfp_add(s->dev, d1, d1, l1, m);
+        sfp_mul_const(s->dev, l0, b0, ka.data(), m);
+        sfp_mul_const(s->dev, l1, b1, ka.data(), m);
+        sfp_add(s->dev, d0, d0, l0, m);
+        sfp_add(s->dev, d1, d1, l1, m);
+        s->stats.or_composed++;
+    }
+    s->stats.constmult += 2;
+    s->stats.tensor++;
+    s->countBytes(7.0 * ell * s->n * 8);  // four rows read, three written per limb (the fused form; modelled)
+    auto r = SfheInternal::relinRescale(this, d0, d1, d2, level, a->slots);
+    r->scale = a->scale * b->scale / (double)s->primes[ell - 1];
+    return SfheInternal::traced(this, r, "EvalGateOr");
+}
+
 // Per column one tensor at q's level over all batches: every (kr - q_b) u_bc
 // carries Delta_q Delta_u, so the batches' tensors are summed as integers
 // before the column's single relinearisation and rescale.  The relinearisations

@@ -445,6 +445,20 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
     std::vector<Ciphertext<DCRTPoly>> EvalWeightSumMany(const std::vector<Ciphertext<DCRTPoly>>& v,
                                                         const std::vector<Plaintext>& p,
                                                         const std::vector<std::vector<Ciphertext<DCRTPoly>>>& u);
+    // Engine extension (the OR of two gates: a join on several keys, DESIGN.md
+    // §4l): a + b - a (.) b, relinearised, one level below the lower operand,
+    // from a single relinearisation and a single rescale.  a and b keep their
+    // own scales Delta_a, Delta_b and may sit at different levels: the one
+    // with more limbs is read over the other's limbs (EvalGateSumMany's rule).
+    // The linear terms enter as kb a + ka b with ka, kb the residues of
+    // Delta_a, Delta_b (formed as EvalLexStep's kr), so the three summands of
+    // the tensor carry Delta_a Delta_b and their sum is exact; the result's
+    // scale field holds Delta_a Delta_b / q_dropped.  The tensor is one launch
+    // where the backend has prims.h sfp_or_tensor; elsewhere (the C oracle,
+    // SFHE_JOIN_FUSED=0 -- read per call --, a level whose rows are dealt over
+    // ranks, or the prim declining) the generic prims compose the same
+    // integers.  OpStats or_fused / or_composed count the calls of each kind.
+    Ciphertext<DCRTPoly> EvalGateOr(const Ciphertext<DCRTPoly>& a, const Ciphertext<DCRTPoly>& b);
     // Engine extension: EvalMult(a_i, b_i) for independent pairs, each formed
     // canonically (rescaled: the values a lazy product takes when its
     // consumer needs the canonical form); pairs at one level run as batched
@@ -824,6 +838,7 @@ class CryptoContextImpl<DCRTPoly> : public std::enable_shared_from_this<CryptoCo
         uint64_t sumn_batches = 0, sumn_fallbacks = 0;
         uint64_t gate_fused = 0, gate_composed = 0;  // EvalGateSumMany calls: tensors fused / composed of generic prims
         uint64_t weight_fused = 0, weight_composed = 0;  // EvalWeightSumMany calls likewise
+        uint64_t or_fused = 0, or_composed = 0;  // EvalGateOr calls: tensor in one launch / composed of generic prims
     };
     OpStats GetOpStats() const;
     void ResetOpStats();
@@ -910,7 +925,7 @@ void RegisterCryptoContext(const CryptoContext<DCRTPoly>& cc);
 // caller's stamp to the library, which throws OpenFHEException on a mismatch.
 // SFHE_LAYOUT_SALT exists only for the test that builds a deliberately
 // mismatched caller (tests/test_abi_stamp.py).
-#define SFHE_FACADE_ABI_VERSION 16
+#define SFHE_FACADE_ABI_VERSION 17
 #ifndef SFHE_LAYOUT_SALT
 #define SFHE_LAYOUT_SALT 0
 #endif

@@ -2322,6 +2322,70 @@ __global__ __launch_bounds__(kThreads) void k_lex_tensor(u64* __restrict__ d0, u
     }
 }
 
+// The join's OR of two gates (prims.h sfp_or_tensor): kb a + ka b - a (.) b
+// before its relinearisation, with na = q - a formed in registers (the
+// canonical residues sfp_neg would have stored):
+//   d0 = kb a0 + ka b0 + na0 b0
+//   d1 = kb a1 + ka b1 + na0 b1 + na1 b0
+//   d2 = na1 b1
+// four rows read and three written per limb.  Each output is ONE reduction of
+// the exact sum of its products, which is the canonical residue the composed
+// form reaches through its reduced intermediates (sfp_tensor, sfp_mul_const,
+// sfp_add), so the two agree residue for residue.  d1 sums four products of
+// canonical residues of primes of at most 60 bits, each below 2^120: less than
+// 2^122, inside the 128-bit accumulator (d0: three, below 3 * 2^120).
+static_assert(2 * sizeof(ConstArgs) + 7 * sizeof(void*) + sizeof(sfp_limbs) + 8 <= 4096,
+              "k_or_tensor's argument block exceeds the 4 KB kernel-argument limit");
+__global__ __launch_bounds__(kThreads) void k_or_tensor(u64* __restrict__ d0, u64* __restrict__ d1,
+                                                        u64* __restrict__ d2, const u64* __restrict__ a0,
+                                                        const u64* __restrict__ a1, const u64* __restrict__ b0,
+                                                        const u64* __restrict__ b1, const ConstArgs ka,
+                                                        const ConstArgs kb, sfp_limbs m,
+                                                        const sf_barrett* __restrict__ bar, uint32_t logn) {
+    // two coefficients per thread (16-byte loads and stores)
+    const size_t pairs = ((size_t)m.count << logn) >> 1;
+    for (size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x; i < pairs;
+         i += (size_t)gridDim.x * kThreads) {
+        const uint32_t limb = (uint32_t)((2 * i) >> logn);
+        const sf_barrett B = loadBar(bar, primeOf(m, limb));
+        const u64 q = B.q, ca = ka.k[limb], cb = kb.k[limb];
+        const ulonglong2 x0 = reinterpret_cast<const ulonglong2*>(a0)[i];
+        const ulonglong2 x1 = reinterpret_cast<const ulonglong2*>(a1)[i];
+        const ulonglong2 y0 = reinterpret_cast<const ulonglong2*>(b0)[i];
+        const ulonglong2 y1 = reinterpret_cast<const ulonglong2*>(b1)[i];
+        ulonglong2 n0, n1;
+        n0.x = sf_neg(x0.x, q);
+        n0.y = sf_neg(x0.y, q);
+        n1.x = sf_neg(x1.x, q);
+        n1.y = sf_neg(x1.y, q);
+        Acc s{0, 0}, t{0, 0}, w{0, 0}, z{0, 0};
+        macc(s, cb, x0.x);  // d0: three products, < 3 * 2^120
+        macc(s, ca, y0.x);
+        macc(s, n0.x, y0.x);
+        macc(t, cb, x0.y);
+        macc(t, ca, y0.y);
+        macc(t, n0.y, y0.y);
+        macc(w, cb, x1.x);  // d1: four products, < 2^122
+        macc(w, ca, y1.x);
+        macc(w, n0.x, y1.x);
+        macc(w, n1.x, y0.x);
+        macc(z, cb, x1.y);
+        macc(z, ca, y1.y);
+        macc(z, n0.y, y1.y);
+        macc(z, n1.y, y0.y);
+        ulonglong2 r0, r1, r2;
+        r0.x = sf_reduce128_acc(s.lo, s.hi, &B);
+        r0.y = sf_reduce128_acc(t.lo, t.hi, &B);
+        r1.x = sf_reduce128_acc(w.lo, w.hi, &B);
+        r1.y = sf_reduce128_acc(z.lo, z.hi, &B);
+        r2.x = bmul(n1.x, y1.x, B);
+        r2.y = bmul(n1.y, y1.y, B);
+        reinterpret_cast<ulonglong2*>(d0)[i] = r0;
+        reinterpret_cast<ulonglong2*>(d1)[i] = r1;
+        reinterpret_cast<ulonglong2*>(d2)[i] = r2;
+    }
+}
+
 // The grouping's gated column sums (prims.h sfp_gate_tensor_cols): for a tile
 // of CT columns and nb <= SFP_GATE_MAX_B batches the tensors of (a0, a1)_b =
 // (kr - q_b0, -q_b1) with (u0, u1)_bc, summed over the batches before any
@@ -6066,6 +6130,38 @@ int sfp_lex_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const u
     SFP_GO(k_lex_tensor, dim3(ewGrid(words / 2)), dim3(kThreads), d0, d1, d2, v0, v1, q0, q1, u0, u1, ka, la, m, d->bar,
            d->logn);
     checkLaunch(d, "lex_tensor");
+    return 0;
+}
+
+int sfp_or_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const uint64_t* a0, const uint64_t* a1,
+                  const uint64_t* b0, const uint64_t* b1, const uint64_t* ka, const uint64_t* kb, sfp_limbs m) {
+    // both constant arrays ride in the kernel's argument block (no upload, no
+    // ring slot: capturable, any lane); 16-byte accesses need aligned rows.
+    // All the checks come before the launch: a decline writes nothing.
+    if (!m.count || m.count > SFP_MAX_LIMBS || d->n < 2) return -1;
+    uint64_t* const outs[3] = {d0, d1, d2};
+    const uint64_t* const ins[4] = {a0, a1, b0, b1};
+    const size_t words = (size_t)m.count * d->n;
+    const uintptr_t bytes = words * 8;
+    for (int k = 0; k < 3; ++k) {
+        const uintptr_t o = (uintptr_t)outs[k];
+        if (!o || (o & 15)) return -1;
+        for (const uint64_t* in : ins)  // (the kernel's pointers are __restrict__)
+            if (o < (uintptr_t)in + bytes && (uintptr_t)in < o + bytes) return -1;
+        for (int j = 0; j < k; ++j)
+            if (o < (uintptr_t)outs[j] + bytes && (uintptr_t)outs[j] < o + bytes) return -1;
+    }
+    for (const uint64_t* in : ins)
+        if (!in || ((uintptr_t)in & 15)) return -1;
+    if (!limbsOk(d, m, "or_tensor")) return -1;
+    ConstArgs ca, cb;
+    std::memcpy(ca.k, ka, m.count * 8);
+    std::memset(ca.k + m.count, 0, (SFP_MAX_LIMBS - m.count) * 8);
+    std::memcpy(cb.k, kb, m.count * 8);
+    std::memset(cb.k + m.count, 0, (SFP_MAX_LIMBS - m.count) * 8);
+    SFP_GO(k_or_tensor, dim3(ewGrid(words / 2)), dim3(kThreads), d0, d1, d2, a0, a1, b0, b1, ca, cb, m, d->bar,
+           d->logn);
+    checkLaunch(d, "or_tensor");
     return 0;
 }
 

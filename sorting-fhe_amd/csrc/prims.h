@@ -437,6 +437,26 @@ SFP_OPTIONAL int sfp_lex_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t
                                 const uint64_t* v1, const uint64_t* q0, const uint64_t* q1, const uint64_t* u0,
                                 const uint64_t* u1, const uint64_t* kr, const uint64_t* lr, sfp_limbs m);
 
+// ---- optional: the OR of two gates (join on several keys) ------------------------
+// With (na0, na1) = (-a0, -a1) -- a and b ciphertexts, ka[limb] and kb[limb]
+// host residues (of a's and of b's scale), all m.count rows in the evaluation
+// domain -- the tensor of na and b plus kb a + ka b in ONE launch:
+//   d0 = kb a0 + ka b0 + na0 b0,  d1 = kb a1 + ka b1 + na0 b1 + na1 b0,  d2 = na1 b1
+// i.e. kb a + ka b - a (.) b before its relinearisation.  na is never stored.
+// The canonical residues of sfp_neg (a0, a1), sfp_tensor(na, b), four
+// sfp_mul_const (kb a0, kb a1, ka b0, ka b1) and four sfp_add: eleven launches.
+// Each output is one reduction of the exact sum of its products (d1: four
+// products of canonical residues of primes of at most 60 bits, under 2^122).
+// ka and kb travel in the kernel's arguments: no upload and no host
+// synchronisation, so the prim may be captured and issued on any lane.  Weak
+// like the prims above: where its address is null (the C oracle), or it returns
+// -1 with nothing written (more than SFP_MAX_LIMBS rows, a row not 16-byte
+// aligned, an output overlapping an input or another output), the host layer
+// runs the generic prims.
+SFP_OPTIONAL int sfp_or_tensor(sfp_dev* d, uint64_t* d0, uint64_t* d1, uint64_t* d2, const uint64_t* a0,
+                               const uint64_t* a1, const uint64_t* b0, const uint64_t* b1, const uint64_t* ka,
+                               const uint64_t* kb, sfp_limbs m);
+
 // ---- optional: the grouping's gated column sums (GROUP BY an encrypted key) ------
 // nb gates q_b (ciphertexts q0[b], q1[b]) shared by nc columns, column c's
 // operand of batch b the ciphertext u0[c * nb + b], u1[c * nb + b]; with

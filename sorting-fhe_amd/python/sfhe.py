@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "sfhe_eval_mult_sum_many", "sfhe_sumn_batch_counts", "sfhe_ct_relabel_scale",
     "sfhe_group_params", "sfhe_sorter_group", "sfhe_eval_gate_sum_many", "sfhe_group_counts",
     "sfhe_window_params", "sfhe_sorter_window", "sfhe_eval_weight_sum_many", "sfhe_window_counts",
+    "sfhe_join_params", "sfhe_sorter_join", "sfhe_eval_gate_or", "sfhe_join_counts",
 ]
 
 MAX_COLUMNS = 8  # SFHE_MAX_COLUMNS
@@ -230,6 +231,10 @@ _SIGS = {
     "sfhe_sorter_window": (C.c_int, [_VP, _VP, _PVP, _SZ, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PVP, _PVP]),
     "sfhe_eval_weight_sum_many": (C.c_int, [_VP, _PVP, _SZ, C.POINTER(_PD), _SZ, _U32, _PVP, _SZ, _PVP]),
     "sfhe_window_counts": (C.c_int, [_VP, _PU64, _PU64]),
+    "sfhe_join_params": (C.c_int, [_U32, _U32, _PU32, _PI32, _SZ, _PSZ]),
+    "sfhe_sorter_join": (C.c_int, [_VP, _PVP, _PVP, _SZ, _PVP, _SZ, C.c_int, C.c_int, C.c_int, _PVP, _PVP]),
+    "sfhe_eval_gate_or": (C.c_int, [_VP, _VP, _VP, _PVP]),
+    "sfhe_join_counts": (C.c_int, [_VP, _PU64, _PU64]),
 }
 
 _libs: dict = {}
@@ -651,6 +656,18 @@ class Engine:
         self._chk(self.lib.sfhe_window_counts(self.ctx, C.byref(f), C.byref(c)))
         return f.value, c.value
 
+    def gate_or(self, a, b):
+        """a + b - a * b (the OR of two 0/1 gates), one level below the lower operand (one
+        relinearisation and one rescale); the operands may sit at different levels."""
+        return self._new(self.lib.sfhe_eval_gate_or, self.ctx, a.h, b.h)
+
+    def join_counts(self):
+        """(fused, composed) gate_or calls (Sorter.join's included) since the last op_stats
+        reset."""
+        f, c = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.sfhe_join_counts(self.ctx, C.byref(f), C.byref(c)))
+        return f.value, c.value
+
     def lex_counts(self):
         """(fused, composed) lex_step tensors (rank_lex's included) since the last op_stats reset."""
         f, c = C.c_uint64(), C.c_uint64()
@@ -1007,6 +1024,28 @@ class Sorter:
         return {"count": Ct(self.eng, cnt) if count else None,
                 "sums": [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cts))]}
 
+    # -- a LEFT JOIN b ON a.k1 = b.k1 [AND ...] --
+    def join(self, keys_a, keys_b, cols_b=(), n: int = 3, dg: int = 2, df: int = 2):
+        """COUNT(b.*) and SUM(b.col) of table A LEFT JOIN table B on 1 to 4 keys, in A's input
+        order: {"count": slot r = rows of B agreeing with A's row r on every key, "sums": [slot r
+        = the column of B summed over those rows]}.  With unique B keys the count is the 0/1
+        semi-join flag (1 - count the anti-join flag) and a sum is the looked-up value; a table
+        joined with itself is GROUP BY k1, ..., km.  Per key, an A value and a B value are equal
+        or at least the sign's resolution apart; both tables occupy N rows.  The context needs
+        join_params' depth for the sign configuration (SfheError otherwise); no placement is
+        evaluated."""
+        keys_a, keys_b, cols_b = list(keys_a), list(keys_b), list(cols_b)
+        if len(keys_a) != len(keys_b):
+            raise SfheError(f"sfhe error -1: {len(keys_a)} keys of table A against {len(keys_b)} of table B")
+        ka = (_VP * max(len(keys_a), 1))(*[k.h if k is not None else None for k in keys_a])
+        kb = (_VP * max(len(keys_b), 1))(*[k.h if k is not None else None for k in keys_b])
+        cs = (_VP * max(len(cols_b), 1))(*[c.h if c is not None else None for c in cols_b])
+        cnt = _VP()
+        outs = (_VP * max(len(cols_b), 1))()
+        self.eng._chk(self.eng.lib.sfhe_sorter_join(self.h, ka, kb, len(keys_a), cs, len(cols_b), n, dg, df,
+                                                    C.byref(cnt), outs))
+        return {"count": Ct(self.eng, cnt), "sums": [Ct(self.eng, C.c_void_p(outs[i])) for i in range(len(cols_b))]}
+
     def top_k(self, ct: Ct, k: int, largest: bool = False, **kw) -> Ct:
         """The k smallest values in ascending order (largest: the k largest, descending)."""
         return self.select(ct, [self.N - 1 - i for i in range(k)] if largest else list(range(k)), **kw)
@@ -1097,6 +1136,20 @@ def group_params(N: int, backend: str = "hip"):
         raise SfheError(lib.sfhe_last_error().decode())
     buf = (C.c_int32 * cnt.value)()
     lib.sfhe_group_params(N, None, buf, cnt.value, None)
+    return depth.value, list(buf)
+
+
+def join_params(N: int, nkeys: int = 1, backend: str = "hip"):
+    """(depth, rotations) for Sorter.join on nkeys keys with N's default sign configuration:
+    group_params' depth plus ceil(log2 nkeys), and the rank's rotation amounts."""
+    lib = load(backend)
+    depth = C.c_uint32()
+    cnt = C.c_size_t()
+    rc = lib.sfhe_join_params(N, nkeys, C.byref(depth), None, 0, C.byref(cnt))
+    if rc != SFHE_OK:
+        raise SfheError(lib.sfhe_last_error().decode())
+    buf = (C.c_int32 * cnt.value)()
+    lib.sfhe_join_params(N, nkeys, None, buf, cnt.value, None)
     return depth.value, list(buf)
 
 
